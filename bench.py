@@ -1,6 +1,11 @@
 """MichiGAN hot-path benchmark: training images/s at 512x512 (G step + D step) on N MI355X.
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR               (+ what the last timed step computed, as DIR/<name>.npy; that step
+                                                          starts again from the seeded initial state, so every run writes the same)
+    python bench.py ... --full                           (+ roofline step, PMC traffic passes, configs[1] leg, CPU baseline)
+
+A plain run sets up, warms up, times K steps and prints the line; everything else it can measure is behind --full.
 
 A "step" = Pix2PixTrainer.run_generator_one_step + run_discriminator_one_step on one synthetic
 batch already resident in HBM (BASELINE.json configs[2]: full G+D+VGG train step, bs=8 per GPU,
@@ -43,11 +48,65 @@ def parse():
                     help="train = G step + D step (headline); gfwd = BASELINE configs[1]: generator forward only, no_grad, train-mode BN")
     ap.add_argument("--inpaint-orient", action="store_true",
                     help="also run the frozen orientation in-painting net in both phases (BASELINE configs[4], --use_ig)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the in-run rocprofv3 --pmc passes behind roofline.traffic (two short child runs of this script)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the BASELINE configs[1] leg (generator forward, fp32, bs 4) reported under `extra`")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: `roofline` (one extra instrumented step + the "
+                         "in-run PMC passes behind roofline.traffic), `extra` (BASELINE configs[1] leg) and `cpu_baseline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (generated images, losses) as DIR/<name>.npy (float32 / float64, <= 64 MB); "
+                         "that step starts again from the seeded initial state (restored off the clock)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip `roofline`")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the in-run rocprofv3 --pmc passes behind roofline.traffic (two short child runs of this script)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the BASELINE configs[1] leg (generator forward, fp32, bs 4) reported under `extra`")
+    a = ap.parse_args()
+    if not a.full:
+        a.no_cpu_baseline = a.no_roofline = a.no_traffic = a.no_extra = True
+    return a
+
+
+DUMP_IMAGE_BYTES = 60 * 1000 * 1000                         # --dump-outputs stays under 64 MB: the losses are a few bytes beside the images
+
+
+def training_state_restorer(trainer, seed: int):
+    """Keep, on the host, every tensor a training step reads and then rewrites -- the optimisers' arenas (weights, Adam moments), the
+    nets' buffers (batch-norm running statistics, spectral-norm vectors) -- and return a function that puts them back, together with the
+    step counters and the host-side RNG.  A step run after it starts from exactly the state the seeds made: its outputs do not carry the
+    run-to-run rounding differences (fp32 atomics in the weight gradients, the two-stream schedule) that every earlier step adds and that
+    training amplifies."""
+    from michigan_amd import parallel
+    opts = (trainer.optimizer_G, trainer.optimizer_D)
+    live = [t for o in opts for t in (o.flat, o.exp_avg, o.exp_avg_sq)] + list(trainer.pix2pix_model.buffers())
+    kept, counts = [t.detach().cpu().clone() for t in live], [o.step_count for o in opts]
+
+    def restore():
+        with torch.no_grad():
+            for t, k in zip(live, kept):
+                t.copy_(k)
+        for o, c in zip(opts, counts):
+            o.step_count = c
+            o.weight_epoch += 1                   # the arena was rewritten: cached packed weights are stale
+        parallel.seed_shared_rng(seed)
+    return restore
+
+
+def dump_outputs(trainer, path: str) -> None:
+    """What a caller of the timed path receives from its last step -- the generated images and every loss -- as path/<name>.npy."""
+    import numpy as np
+    out = {}
+    gen = trainer.get_latest_generated()
+    if gen is not None:
+        g = gen.detach().float().cpu().numpy()
+        if g.nbytes > DUMP_IMAGE_BYTES:
+            # a fixed sample (seeded by nothing but the shape) of the flattened images, in index order
+            idx = np.sort(np.random.default_rng(g.size).choice(g.size, DUMP_IMAGE_BYTES // 4, replace=False))
+            out["generated_sample"] = g.reshape(-1)[idx]
+        else:
+            out["generated"] = g
+    for k, v in trainer.get_latest_losses().items():
+        out["loss_" + k] = np.asarray(float(v.detach().double()), dtype=np.float64).reshape(1)
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def _streams_on() -> bool:
@@ -283,6 +342,12 @@ def main():
     def barrier():
         dist.barrier(device_ids=[local]) if backend == "nccl" else dist.barrier()
 
+    from michigan_amd import parallel
+    host_seed = 1234
+    parallel.seed_shared_rng(host_seed)                     # the encoder's host-side draw per forward: identical work in every run with the same arguments
+    # --dump-outputs: the last timed step starts again from the state the seeds made, so that what it computes is the same in every run
+    # with the same arguments; the restore itself (host -> device copies) is kept off the clock
+    restore = training_state_restorer(trainer, host_seed) if a.dump_outputs else None
     for _ in range(a.warmup):
         step()
     if world > 1:
@@ -290,13 +355,22 @@ def main():
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    paused = 0.0
+    for i in range(a.steps):
+        if restore is not None and i == a.steps - 1:
+            torch.cuda.synchronize()
+            tp = time.perf_counter()
+            restore()
+            torch.cuda.synchronize()
+            if world > 1:
+                barrier()
+            paused += time.perf_counter() - tp
         step()
     torch.cuda.synchronize()
-    dt_own = time.perf_counter() - t0                         # this rank alone: when ITS last kernel finished (before the closing barrier)
+    dt_own = time.perf_counter() - t0 - paused                # this rank alone: when ITS last kernel finished (before the closing barrier)
     if world > 1:
         barrier()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - paused
     per_rank_ms = None
     if world > 1:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
@@ -306,6 +380,8 @@ def main():
         own[rank] = dt_own / a.steps * 1e3
         dist.all_reduce(own)                                    # every rank's own ms/step: the spread shows a straggler / a stalled communicator
         per_rank_ms = [round(v, 3) for v in own.tolist()]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(trainer, a.dump_outputs)
     peak_mem = {"timed_region": round(torch.cuda.max_memory_allocated() / 1e9, 2)}     # the side stream keeps operands referenced longer
     losses = {k: float(v.detach().float().mean()) for k, v in trainer.get_latest_losses().items()}
     step_gflop_ref = STEP_GFLOP_REFERENCE if a.mode == "train" else F_G

@@ -181,8 +181,81 @@ def make_config0():
           "fixture %.2f MB" % (os.path.getsize(os.path.join(OUT, "config0_67172.npz")) / 1e6))
 
 
+def _ellipse_mask(h, w, seed):
+    r = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    cy, cx = h / 2 + r.uniform(-h / 8, h / 8), w / 2 + r.uniform(-w / 8, w / 8)
+    return ((((yy - cy) / (h * r.uniform(0.2, 0.35))) ** 2 + ((xx - cx) / (w * r.uniform(0.2, 0.35))) ** 2) <= 1).astype(np.uint8)
+
+
+def make_inputs():
+    """tests/golden/inputs_reference.npz: the loader functions of data/base_dataset.py (generate_hole with its random draws pinned,
+    trans_orient_to_rgb, generate_noise with its normal fields recorded) on the inputs tests/test_inputs.py feeds the oracle."""
+    from oracle import inputs_oracle as IO
+    os.environ.setdefault("MPLBACKEND", "Agg")
+    R.setup()
+    import cv2
+    cv2.resize = lambda src, dsize=None, **k: IO.cv2_resize_linear(src, dsize)      # cv2 is absent: see inputs_oracle header
+    if not hasattr(np, "float"):
+        np.float = float                                                         # base_dataset.py:358 (numpy < 1.24 alias)
+    import data.base_dataset as bd
+    fx = {}
+    saved = (random.uniform, random.randint, np.random.normal)          # bd.random / bd.np.random are these modules
+    try:
+        for seed in (0, 1, 2):
+            h, w = 96, 80
+            mask = _ellipse_mask(h, w, seed)
+            omask = _ellipse_mask(h, w, seed + 100) if seed else mask.copy()          # seed 0: orient_mask == mask (step 1)
+            nums = int((omask != 0).sum())
+            th, ci = 0.5 + 0.35 * seed, (nums * (seed + 1)) // 4
+            random.uniform, random.randint = (lambda a, b: th), (lambda a, b: ci)
+            fx["hole%d_mask" % seed], fx["hole%d_omask" % seed] = mask, omask
+            fx["hole%d_want" % seed] = np.array(bd.generate_hole(mask, omask))
+        random.uniform, random.randint = saved[:2]
+        fx["hole_empty_want"] = np.array(bd.generate_hole(_ellipse_mask(16, 16, 3), np.zeros((16, 16), np.uint8)))
+        orient = np.arange(256, dtype=np.uint8).reshape(16, 16).repeat(2, 0).repeat(2, 1)
+        fx["orient_rgb_want"] = np.array(bd.trans_orient_to_rgb(orient, _ellipse_mask(32, 32, 5)))
+        rs, fields = np.random.RandomState(11), []
+
+        def normal(loc, scale, size):
+            f = rs.normal(loc=loc, scale=scale, size=size)
+            fields.append(f)
+            return f
+        np.random.normal = normal
+        fx["noise_want"] = np.asarray(bd.generate_noise(64, 64))
+        for i, fld in enumerate(fields):
+            fx["noise_field%d" % i] = fld
+    finally:
+        random.uniform, random.randint, np.random.normal = saved
+    np.savez_compressed(os.path.join(OUT, "inputs_reference.npz"), **fx)
+
+
+def make_oracle():
+    """tests/golden/oracle_reference.npz: reference modules the CPU oracle is pinned to, on small seeded inputs -- the in-painting
+    net (tests/test_inpaint.py) and the Gabor orientation loss (tests/test_oracle.py)."""
+    R.setup()
+    fx = {}
+    ig = R.build_inpaint(R.make_opt()).eval()
+    ig.load_state_dict(synth_state_dict(ig.state_dict(), seed=3, gain=1.0))
+    x = torch.rand(1, 4, 32, 32, generator=torch.Generator().manual_seed(4))
+    with torch.no_grad():
+        fx["inpaint_out"] = ig(x).numpy()
+    b = synth_batch(2, 64, seed=3)
+    crit = R.losses().L1OLoss(R.make_opt(crop_size=64, orient_filter="gabor"))
+    fake = torch.tanh(torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(4)))
+    want_o, want_c = crit(fake, b["orient"], b["input_tag"])
+    fx["orient_loss"] = np.array([float(want_o), float(want_c)])
+    np.savez_compressed(os.path.join(OUT, "oracle_reference.npz"), **fx)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if "--inputs" in sys.argv:             # only this fixture
+        make_inputs()
+        return
+    if "--oracle" in sys.argv:             # only this fixture
+        make_oracle()
+        return
     if "--config0" in sys.argv:
         make_config0()
         return

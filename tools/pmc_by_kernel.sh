@@ -5,7 +5,7 @@
 # durations come from a third, counter-free kernel-trace pass of the same command.
 set -u
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/pmc_by_kernel; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-CMD="python $R/bench.py --steps 1 --warmup 1 --no-roofline --no-cpu-baseline"
+CMD="python $R/bench.py --full --steps 1 --warmup 1 --no-roofline --no-cpu-baseline"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$c -o p -- $CMD > $OUT/$c.log 2>&1
 done

@@ -6,10 +6,11 @@
 # 64 B, so the read side is doubled; units are KiB.
 set -u
 COMMIT=${1:-unknown}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_step
 mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$c -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-roofline --no-cpu-baseline > $OUT/$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$c -o p -- python $R/bench.py --full --steps 1 --warmup 1 --no-roofline --no-cpu-baseline > $OUT/$c.log 2>&1
 done
 python - <<PY
 import csv, glob, json

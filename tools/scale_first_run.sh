@@ -11,9 +11,9 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 line() {   # name, N, env...
     local name=$1 n=$2; shift 2
     local log="$OUT/${name}_n${n}.json"
-    if [ "$n" = 1 ]; then env "$@" python bench.py --gpus 1 --steps "$STEPS" --warmup 3 --batch-per-gpu "$BPG" --no-cpu-baseline --no-traffic --no-extra 2>"$log.err" | tail -1 > "$log"
+    if [ "$n" = 1 ]; then env "$@" python bench.py --full --gpus 1 --steps "$STEPS" --warmup 3 --batch-per-gpu "$BPG" --no-cpu-baseline --no-traffic --no-extra 2>"$log.err" | tail -1 > "$log"
     else env "$@" python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 500)) \
-             bench.py --gpus "$n" --steps "$STEPS" --warmup 3 --batch-per-gpu "$BPG" --no-cpu-baseline --no-traffic --no-extra 2>"$log.err" | tail -1 > "$log"; fi
+             bench.py --full --gpus "$n" --steps "$STEPS" --warmup 3 --batch-per-gpu "$BPG" --no-cpu-baseline --no-traffic --no-extra 2>"$log.err" | tail -1 > "$log"; fi
     python - "$name" "$n" "$log" <<'PY'
 import json, sys
 name, n, path = sys.argv[1:4]
@@ -26,7 +26,7 @@ except Exception as e:
     print(f"{name:28s} N={n}  FAILED ({e}); see {path}.err")
 PY
 }
-echo "# bench.py --batch-per-gpu $BPG --steps $STEPS on $NGPU GPU(s); default = one communicator, in-stream sync-BN, grad buckets on the process group's stream, weight gradients + the generator step's D branch / VGG(real) on the second stream"
+echo "# bench.py --full --batch-per-gpu $BPG --steps $STEPS on $NGPU GPU(s); default = one communicator, in-stream sync-BN, grad buckets on the process group's stream, weight gradients + the generator step's D branch / VGG(real) on the second stream"
 line default 1
 for N in 2 4 8; do
     [ "$N" -le "$NGPU" ] || continue
