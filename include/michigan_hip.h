@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MG_ABI_VERSION 6
+#define MG_ABI_VERSION 7
 
 enum { MG_F32 = 0, MG_BF16 = 1 };
 enum { MG_ACT_NONE = 0, MG_ACT_RELU = 1, MG_ACT_LRELU = 2, MG_ACT_TANH = 3 };
@@ -474,6 +474,28 @@ int mg_orient_loss_fwd(const float* conf_raw, const uint8_t* idx, const float* l
 int mg_orient_loss_bwd(const float* conf_raw, const uint8_t* idx, const float* label, int32_t label_ch, int64_t label_nstride,
                        const float* hair, int64_t hair_nstride, const float* g_orient, const float* g_conf, const float* fwd_out,
                        int32_t N, int64_t HW, float* dconf, void* stream);
+
+/* The image-space L1 terms of the generator objective in one pass over the generated and the target image (mg_color_loss.hip):
+ * LabColorLoss.forward (loss.py:403-532, called at pix2pix_model.py:331-336; balance_Lab off), criterionRGBL1 = nn.L1Loss
+ * (pix2pix_model.py:324-329) and RGBBackgroundL1Loss.forward (loss.py:388-400, called at pix2pix_model.py:317-322).
+ * img: the generated image, NHWC [N,H,W,C] in `dtype` with RGB in channels 0..2 (C >= 3; the layout of mg_gabor_argmax_fwd); real: the
+ * target, fp32, three dense planes [H,W] per sample, sample n at real + n * real_nstride; back: the background plane m (channel 0 of the
+ * one-hot label) of sample n at back + n * back_nstride, may be NULL when bit 2 of `flags` is clear.  Both images in [-1, 1]; per pixel
+ * rgb01 = (x + 1) / 2, XYZ = M rgb01 with each row of the matrix of loss.py:409 divided by its row sum, f(t) = cbrt(t) for
+ * t > 0.008856 else 7.787 t + 0.137931, a = 500 (f(X) - f(Y)), b = 200 (f(Y) - f(Z)).  `flags` selects the terms (a term not selected
+ * costs nothing and reads nothing):
+ *   bit 0  out[0] = lab        = mean(|a_f - a_r| + |b_f - b_r|) over N*2*H*W
+ *   bit 1  out[1] = rgb        = mean |x_f - x_r| over N*3*H*W
+ *   bit 2  out[2] = background = mean |x_f m - x_r m| over N*3*H*W (not divided by sum m)
+ * out: 3 floats, 0 for a term not selected.  ws: >= 3072 floats (one partial per workgroup and term; summed in a fixed order in double,
+ * so the result is bit-reproducible).  All arithmetic fp32.
+ * bwd: dimg = d(g_lab[0] out[0] + g_rgb[0] out[1] + g_back[0] out[2]) / d img in the image's dtype and layout, channels 3..C-1 zero;
+ * the g_* are device scalars, a NULL pointer = 0; d|u|/du = sign(u) with sign(0) = 0.  The target image gets no gradient. */
+int mg_color_loss_fwd(const void* img, const float* real, int64_t real_nstride, const float* back, int64_t back_nstride,
+                      int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flags, float* out, float* ws, void* stream);
+int mg_color_loss_bwd(const void* img, const float* real, int64_t real_nstride, const float* back, int64_t back_nstride,
+                      const float* g_lab, const float* g_rgb, const float* g_back,
+                      int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flags, void* dimg, void* stream);
 
 /* ---------------------------------------------------------------------------
  * (iv) Collectives over RCCL / xGMI -- SURVEY.md section 8b's last export group.  One communicator per process (= per GPU); what the

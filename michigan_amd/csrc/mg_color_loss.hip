@@ -1,0 +1,206 @@
+// mg_color_loss.hip -- the image-space L1 terms of the generator objective as one fused pass (reference:
+// models/networks/loss.py:388-400 RGBBackgroundL1Loss, :403-532 LabColorLoss, models/pix2pix_model.py:317-336).
+//
+// The three terms read the same two images: the generated one (NHWC, RGB in channels 0..2, what the generator's last
+// convolution wrote) and the target (NCHW fp32, what the loader gives).  Per pixel and image: rgb01 = (x + 1) / 2, XYZ by the
+// row-normalised sRGB matrix, f(t) = cbrt(t) above 0.008856 and 7.787 t + 0.137931 below, a = 500 (f(X) - f(Y)),
+// b = 200 (f(Y) - f(Z)) -- L never enters the loss and is not computed.
+//   color_loss_partial_kernel   per-workgroup partial sums of |da| + |db|, sum_c |dx_c| and sum_c |dx_c * m| into the workspace
+//   color_loss_final_kernel     sums the partials in a fixed order in double, scales to the three means (no float atomics:
+//                               the result is bit-reproducible from run to run)
+//   color_loss_bwd_kernel       dimg = g_lab dlab + g_rgb drgb + g_back dback in the image's dtype and layout, padding channels zero
+// The eager spelling is ~40 launches per call, six of them boolean-mask index assignments that synchronise the host; the
+// data is ~50 MB per step at 8 x 512^2, so one coalesced read of each operand is all there is to do here.
+#include "mg_common.h"
+
+// No fused multiply-add contraction in this file: a - b of two products that are equal must be exactly 0 (sign(0) = 0 where the
+// generated pixel equals the target), and a contracted fma(x, y, -round(x * y)) would leave the product's rounding error instead.
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int CL_BLOCKS = 1024;                                   // rows of the workspace: ws[term * CL_BLOCKS + block]
+constexpr float CL_KNEE = 0.008856f, CL_LIN = 7.787f, CL_OFF = 0.137931f;
+// loss.py:409 (an fp32 tensor there, hence the f suffixes), each row divided by its row sum (rgb2xyz, loss.py:446-464)
+constexpr float CL_M[3][3] = {{0.412453f, 0.357580f, 0.180423f}, {0.212671f, 0.715160f, 0.072169f}, {0.019334f, 0.119193f, 0.950227f}};
+constexpr float cl_m(int r, int c) { return (float)((double)CL_M[r][c] / ((double)CL_M[r][0] + (double)CL_M[r][1] + (double)CL_M[r][2])); }
+
+__device__ __forceinline__ float cl_f(float t) { return t > CL_KNEE ? cbrtf(t) : CL_LIN * t + CL_OFF; }
+__device__ __forceinline__ float cl_df(float t) { if (t > CL_KNEE) { const float c = cbrtf(t); return 1.f / (3.f * c * c); } return CL_LIN; }
+__device__ __forceinline__ float cl_sign(float u) { return u > 0.f ? 1.f : (u < 0.f ? -1.f : 0.f); }
+
+__device__ __forceinline__ void cl_xyz(const float x[3], float xyz[3])
+{
+    const float r = (x[0] + 1.f) * 0.5f, g = (x[1] + 1.f) * 0.5f, b = (x[2] + 1.f) * 0.5f;
+    xyz[0] = cl_m(0, 0) * r + cl_m(0, 1) * g + cl_m(0, 2) * b;
+    xyz[1] = cl_m(1, 0) * r + cl_m(1, 1) * g + cl_m(1, 2) * b;
+    xyz[2] = cl_m(2, 0) * r + cl_m(2, 1) * g + cl_m(2, 2) * b;
+}
+
+__device__ __forceinline__ void cl_ab(const float x[3], float& a, float& b)
+{
+    float xyz[3];
+    cl_xyz(x, xyz);
+    const float fx = cl_f(xyz[0]), fy = cl_f(xyz[1]), fz = cl_f(xyz[2]);
+    a = 500.f * (fx - fy);
+    b = 200.f * (fy - fz);
+}
+
+// RGB of one generated pixel: one 8- or 16-byte load when the pixel is quad-aligned (the generator's padded output), else three scalars
+template <typename T>
+__device__ __forceinline__ void cl_load_rgb(const T* __restrict__ p, int C, float x[3])
+{
+    if ((C & 3) == 0) { const f32x4_t v = ET<T>::load4(p); x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; }
+    else { x[0] = ET<T>::load1(p); x[1] = ET<T>::load1(p + 1); x[2] = ET<T>::load1(p + 2); }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void color_loss_partial_kernel(const T* __restrict__ img, const float* __restrict__ real, int64_t real_nstride,
+                                                                 const float* __restrict__ back, int64_t back_nstride, int N, int64_t HW, int C,
+                                                                 int flags, float* __restrict__ ws)
+{
+    __shared__ float red[3][4];
+    float s_lab = 0.f, s_rgb = 0.f, s_bg = 0.f;
+    const int64_t total = (int64_t)N * HW;
+    for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int n = (int)(i / HW);
+        const int64_t pix = i - (int64_t)n * HW;
+        const float* __restrict__ rp = real + (int64_t)n * real_nstride + pix;
+        float xf[3], xr[3];
+        cl_load_rgb(img + i * C, C, xf);
+        xr[0] = rp[0]; xr[1] = rp[HW]; xr[2] = rp[2 * HW];
+        if (flags & 1) {
+            float af, bf, ar, br;
+            cl_ab(xf, af, bf);
+            cl_ab(xr, ar, br);
+            s_lab += fabsf(af - ar) + fabsf(bf - br);
+        }
+        if (flags & 2) s_rgb += fabsf(xf[0] - xr[0]) + fabsf(xf[1] - xr[1]) + fabsf(xf[2] - xr[2]);
+        if (flags & 4) {
+            const float m = back[(int64_t)n * back_nstride + pix];
+            s_bg += fabsf(xf[0] * m - xr[0] * m) + fabsf(xf[1] * m - xr[1] * m) + fabsf(xf[2] * m - xr[2] * m);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s_lab += __shfl_down(s_lab, o, 64); s_rgb += __shfl_down(s_rgb, o, 64); s_bg += __shfl_down(s_bg, o, 64); }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s_lab; red[1][threadIdx.x >> 6] = s_rgb; red[2][threadIdx.x >> 6] = s_bg; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        float t = 0.f;
+        for (int w = 0; w < 4; ++w) t += red[threadIdx.x][w];
+        ws[threadIdx.x * CL_BLOCKS + blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(256) void color_loss_final_kernel(const float* __restrict__ ws, int nblk, double inv_lab, double inv_rgb, float* __restrict__ out)
+{
+    __shared__ double red[3][256];
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < nblk; i += 256)
+        for (int q = 0; q < 3; ++q) s[q] += (double)ws[q * CL_BLOCKS + i];
+    for (int q = 0; q < 3; ++q) red[q][threadIdx.x] = s[q];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[0] = (float)(red[0][0] * inv_lab);                      // nn.L1Loss over Lab channels 1: -> N*2*H*W elements
+        out[1] = (float)(red[1][0] * inv_rgb);                      // nn.L1Loss over N*3*H*W
+        out[2] = (float)(red[2][0] * inv_rgb);                      // NOT divided by sum(m) (loss.py:393-400)
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void color_loss_bwd_kernel(const T* __restrict__ img, const float* __restrict__ real, int64_t real_nstride,
+                                                             const float* __restrict__ back, int64_t back_nstride,
+                                                             const float* __restrict__ g_lab, const float* __restrict__ g_rgb,
+                                                             const float* __restrict__ g_back, int N, int64_t HW, int C, int flags,
+                                                             T* __restrict__ dimg)
+{
+    const int64_t total = (int64_t)N * HW;
+    // d mean / d element, and the /2 of rgb01 for the Lab chain
+    const float gl = (flags & 1) && g_lab ? g_lab[0] * (float)(0.5 / (2.0 * (double)total)) : 0.f;
+    const float gr = (flags & 2) && g_rgb ? g_rgb[0] * (float)(1.0 / (3.0 * (double)total)) : 0.f;
+    const float gb = (flags & 4) && g_back ? g_back[0] * (float)(1.0 / (3.0 * (double)total)) : 0.f;
+    for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int n = (int)(i / HW);
+        const int64_t pix = i - (int64_t)n * HW;
+        const float* __restrict__ rp = real + (int64_t)n * real_nstride + pix;
+        float xf[3], xr[3], d[3] = {0.f, 0.f, 0.f};
+        cl_load_rgb(img + i * C, C, xf);
+        xr[0] = rp[0]; xr[1] = rp[HW]; xr[2] = rp[2 * HW];
+        if (flags & 1) {
+            float xyz[3], ar, br;
+            cl_xyz(xf, xyz);
+            cl_ab(xr, ar, br);
+            const float fx = cl_f(xyz[0]), fy = cl_f(xyz[1]), fz = cl_f(xyz[2]);
+            const float sa = 500.f * cl_sign(500.f * (fx - fy) - ar), sb = 200.f * cl_sign(200.f * (fy - fz) - br);
+            // dL/dX, dL/dY, dL/dZ, then through the matrix rows
+            const float dX = gl * sa * cl_df(xyz[0]), dY = gl * (sb - sa) * cl_df(xyz[1]), dZ = -gl * sb * cl_df(xyz[2]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d[c] = dX * cl_m(0, c) + dY * cl_m(1, c) + dZ * cl_m(2, c);
+        }
+        if (flags & 2) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d[c] += gr * cl_sign(xf[c] - xr[c]);
+        }
+        if (flags & 4) {
+            const float m = back[(int64_t)n * back_nstride + pix];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d[c] += gb * m * cl_sign(xf[c] * m - xr[c] * m);
+        }
+        T* __restrict__ o = dimg + i * C;
+        if ((C & 3) == 0) {
+            const f32x4_t v = {d[0], d[1], d[2], 0.f}, z = {0.f, 0.f, 0.f, 0.f};
+            ET<T>::store4(o, v);
+            for (int c = 4; c < C; c += 4) ET<T>::store4(o + c, z);
+        } else {
+            ET<T>::store1(o, d[0]); ET<T>::store1(o + 1, d[1]); ET<T>::store1(o + 2, d[2]);
+            for (int c = 3; c < C; ++c) ET<T>::store1(o + c, 0.f);
+        }
+    }
+}
+
+inline int cl_grid(int64_t pixels, int cap) { const int64_t g = (pixels + 255) / 256; return (int)(g > cap ? cap : g); }
+
+}  // namespace
+
+#define MG_COLOR_CHECK(name) \
+    MG_CHECK_ARG(dtype == MG_F32 || dtype == MG_BF16, name ": bad dtype"); \
+    MG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C >= 3, name ": bad geometry N=%d H=%d W=%d C=%d", N, H, W, C); \
+    MG_CHECK_ARG(flags >= 1 && flags <= 7, name ": flags must select at least one of lab (1), rgb (2), background (4)"); \
+    MG_CHECK_ARG(real_nstride >= 3 * (int64_t)H * W, name ": the target image needs three dense planes per sample"); \
+    MG_CHECK_ARG(!(flags & 4) || (back && back_nstride >= (int64_t)H * W), name ": the background term needs the label plane")
+
+extern "C" int mg_color_loss_fwd(const void* img, const float* real, int64_t real_nstride, const float* back, int64_t back_nstride,
+                                 int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flags, float* out, float* ws, void* stream)
+{
+    MG_CHECK_ARG(img && real && out && ws, "mg_color_loss_fwd: null pointer");
+    MG_COLOR_CHECK("mg_color_loss_fwd");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t HW = (int64_t)H * W;
+    const int grid = cl_grid((int64_t)N * HW, CL_BLOCKS);
+    if (dtype == MG_BF16) hipLaunchKernelGGL(color_loss_partial_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, (const uint16_t*)img, real, real_nstride, back, back_nstride, N, HW, C, flags, ws);
+    else hipLaunchKernelGGL(color_loss_partial_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)img, real, real_nstride, back, back_nstride, N, HW, C, flags, ws);
+    MG_CHECK_LAUNCH("mg_color_loss_fwd");
+    const double cnt = (double)N * (double)HW;
+    hipLaunchKernelGGL(color_loss_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, grid, 1.0 / (2.0 * cnt), 1.0 / (3.0 * cnt), out);
+    MG_CHECK_LAUNCH("mg_color_loss_fwd(final)");
+    return MG_OK;
+}
+
+extern "C" int mg_color_loss_bwd(const void* img, const float* real, int64_t real_nstride, const float* back, int64_t back_nstride,
+                                 const float* g_lab, const float* g_rgb, const float* g_back,
+                                 int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flags, void* dimg, void* stream)
+{
+    MG_CHECK_ARG(img && real && dimg, "mg_color_loss_bwd: null pointer");
+    MG_COLOR_CHECK("mg_color_loss_bwd");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t HW = (int64_t)H * W;
+    const int grid = cl_grid((int64_t)N * HW, 4096);
+    if (dtype == MG_BF16) hipLaunchKernelGGL(color_loss_bwd_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, (const uint16_t*)img, real, real_nstride, back, back_nstride, g_lab, g_rgb, g_back, N, HW, C, flags, (uint16_t*)dimg);
+    else hipLaunchKernelGGL(color_loss_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)img, real, real_nstride, back, back_nstride, g_lab, g_rgb, g_back, N, HW, C, flags, (float*)dimg);
+    MG_CHECK_LAUNCH("mg_color_loss_bwd");
+    return MG_OK;
+}

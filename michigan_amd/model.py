@@ -4,8 +4,11 @@
 run_discriminator_one_step` keep the reference's names and call structure
 (models/pix2pix_model.py:62-93,257-398, trainers/pix2pix_trainer.py:39-77) for the losses that
 sit on the hot path under the README flags:  hinge GAN (wide_edge), discriminator feature
-matching, VGG perceptual loss and the Gabor orientation loss (on by default in the reference).  The Lab /
-style / background losses and the frozen in-painting net are outside this tier's scope.
+matching, VGG perceptual loss and the Gabor orientation loss (on by default in the reference), and the image-space
+Lab colour / RGB / background L1 terms (pix2pix_model.py:317-336) as one fused pass.  The published training recipe keeps
+the Lab term ON (`no_lab_loss=False`); `default_options()` leaves the three terms off because the committed fixtures and
+the benchmark's history were recorded without them.  Style / content, HairAvgLab, balance_Lab and the blender are outside
+this tier's scope.
 
 Differences that do not change results (SURVEY.md section 8a "parity-preserving minimum"):
   * the discriminator's parameters do not require grad during the generator step (their
@@ -60,6 +63,10 @@ def default_options(**over) -> argparse.Namespace:
         # run the frozen in-painting net on (hole, orient_rgb, noise) like the reference does under --use_ig
         # (pix2pix_model.py:260-263); off by default: BASELINE configs[1-3] feed the orientation map directly
         netIG="inpaint", inpaint_orient=False,
+        # image-space L1 terms (pix2pix_model.py:317-336).  The README recipe is no_lab_loss=False (lambda_lab 1); all three stay off
+        # here so that the recorded fixtures and benchmark numbers keep their objective -- switch them on per run
+        no_lab_loss=True, no_rgb_loss=True, no_background_loss=True, lambda_lab=1.0, lambda_rgb=1.0, lambda_background=1.0,
+        balance_Lab=False,
     )
     d.update(over)
     return argparse.Namespace(**d)
@@ -81,6 +88,8 @@ class Pix2PixModel(nn.Module):
                     self.criterionVGG.vgg.compute_dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}.get(dt, dt)
             if not getattr(opt, "no_orient_loss", True):
                 self.criterionOrient = networks.L1OLoss(opt)
+            if not getattr(opt, "no_lab_loss", True) and getattr(opt, "balance_Lab", False):
+                raise NotImplementedError("Lab colour loss: the balance_Lab weighting is not implemented")
         self.netIG = None
         if getattr(opt, "inpaint_orient", False):
             self.netIG = networks.define_IG(opt).eval()          # frozen (pix2pix_model.py:196-198)
@@ -297,6 +306,19 @@ class Pix2PixModel(nn.Module):
             losses["ORIENT"] = _scaled(orient, self.opt.lambda_orient)
             if not self.opt.no_confidence_loss:
                 losses["CONFIDENCE"] = conf * self.opt.lambda_confidence
+        if self.opt.curr_step == 1 and ref_is_tag:
+            # background / rgb / lab (pix2pix_model.py:317-336): ONE pass over (fake, image_tag) for whichever of the three are enabled
+            flags = ((0 if getattr(self.opt, "no_lab_loss", True) else ops.COLOR_LAB)
+                     | (0 if getattr(self.opt, "no_rgb_loss", True) else ops.COLOR_RGB)
+                     | (0 if getattr(self.opt, "no_background_loss", True) else ops.COLOR_BACKGROUND))
+            if flags:
+                lab, rgb, back = ops.color_losses(fake.permute(0, 2, 3, 1), d["image_tag"], d["input_tag"].detach()[:, 0], flags)
+                if flags & ops.COLOR_BACKGROUND:
+                    losses["background"] = _scaled(back, getattr(self.opt, "lambda_background", 1.0))
+                if flags & ops.COLOR_RGB:
+                    losses["rgb"] = _scaled(rgb, getattr(self.opt, "lambda_rgb", 1.0))
+                if flags & ops.COLOR_LAB:
+                    losses["lab"] = _scaled(lab, getattr(self.opt, "lambda_lab", 1.0))
         if branch:
             main.wait_stream(side)                                # the D branch's loss scalars are summed on the main stream
             for k in ("GAN", "GAN_Feat") + (("ORIENT", "CONFIDENCE") if int(ops.BRANCH_STREAMS) >= 3 else ()):

@@ -2,7 +2,8 @@
 
 Reductions run in fp32 on whatever dtype the discriminator / VGG towers produced, as fused HIP launches: the hinge GAN
 loss with its wide-edge weight mask (mg_hinge_*, mg_wide_edge_weight), discriminator feature matching and the VGG taps
-(mg_l1_mean_*), the Gabor orientation loss (mg_gabor_argmax_*).  Lab / style / background losses are out of scope
+(mg_l1_mean_*), the Gabor orientation loss (mg_gabor_argmax_*), and the image-space Lab colour / background / RGB L1
+terms as one pass (mg_color_loss_*).  Style / content, HairAvgLab and the balance_Lab weighting are out of scope
  and stay the reference's own classes under michigan_amd.dropin."""
 from __future__ import annotations
 
@@ -208,3 +209,34 @@ class L1OLoss(nn.Module):
         conf = torch.clamp(confidence, 0.001, 1)
         confidence_loss = -torch.sum(torch.log(conf) * hair) / torch.sum(hair)
         return orient_loss, confidence_loss
+
+
+def _image_nhwc(fake):
+    """The generated image as the kernels read it: the generator's NHWC-backed NCHW view is aliased (zero-copy), a plain
+    contiguous NCHW image costs one permute().contiguous()."""
+    if fake.dtype not in (torch.float32, torch.bfloat16):
+        fake = fake.float()
+    return fake.permute(0, 2, 3, 1)
+
+
+class RGBBackgroundL1Loss(nn.Module):
+    """L1 between the generated and the target image outside the hair region (reference: loss.py:388-400): mean over
+    N*3*H*W of |fake * m - image * m|, m = channel 0 of the one-hot label; not divided by the area of m."""
+
+    def forward(self, fake, input_semantics, image_tag):
+        return ops.color_losses(_image_nhwc(fake), image_tag, input_semantics.detach()[:, 0], ops.COLOR_BACKGROUND)[2]
+
+
+class LabColorLoss(nn.Module):
+    """L1 between the a and b channels of the generated and the target image in CIE Lab (reference: loss.py:403-532,
+    the rgb2xyz / xyz2lab route; L is not part of the loss).  `opt.balance_Lab` (a histogram-weighted variant that
+    needs `opt.weight_dir`) is not implemented."""
+
+    def __init__(self, opt):
+        super().__init__()
+        if getattr(opt, "balance_Lab", False):
+            raise NotImplementedError("Lab colour loss: the balance_Lab weighting is not implemented")
+        self.opt = opt
+
+    def forward(self, fake, real, mask=None):
+        return ops.color_losses(_image_nhwc(fake), real, None, ops.COLOR_LAB)[0]

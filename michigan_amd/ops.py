@@ -1809,6 +1809,70 @@ def orient_loss(conf_raw: torch.Tensor, idx: torch.Tensor, label: torch.Tensor, 
     return _OrientLossFn.apply(conf_raw.contiguous(), idx.contiguous(), label, hair)
 
 
+COLOR_LAB, COLOR_RGB, COLOR_BACKGROUND = 1, 2, 4      # `flags` bits of mg_color_loss_*
+
+
+class _ColorLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, real, back, flags):
+        img = _nhwc(img)
+        n, h, w, c = img.shape
+        out = torch.empty(3, dtype=torch.float32, device=img.device)
+        ws = torch.empty(3 * 1024, dtype=torch.float32, device=img.device)
+        bp, bs = _plane_args(back) if back is not None else (None, 0)
+        C.backend().mg_color_loss_fwd(_p(img), _p(real), real.stride(0), bp, bs, _dt(img), n, h, w, c, flags, _p(out), _p(ws), _stream(img))
+        ctx.save_for_backward(img, real, back)
+        ctx.flags = flags
+        ctx.set_materialize_grads(False)
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    def backward(ctx, g_lab, g_rgb, g_back):
+        img, real, back = ctx.saved_tensors
+        if g_lab is None and g_rgb is None and g_back is None:
+            return None, None, None, None
+        n, h, w, c = img.shape
+        fix = lambda g: None if g is None else (g if g.dtype == torch.float32 else g.float())
+        g_lab, g_rgb, g_back = fix(g_lab), fix(g_rgb), fix(g_back)
+        bp, bs = _plane_args(back) if back is not None else (None, 0)
+        d = torch.empty_like(img)
+        C.backend().mg_color_loss_bwd(_p(img), _p(real), real.stride(0), bp, bs, _p(g_lab), _p(g_rgb), _p(g_back), _dt(img), n, h, w, c,
+                                      ctx.flags, _p(d), _stream(img))
+        return d, None, None, None
+
+
+def color_losses(fake: torch.Tensor, real: torch.Tensor, back: Optional[torch.Tensor], flags: int):
+    """(lab, rgb, background) of the generator objective (LabColorLoss loss.py:403-532 without balance_Lab, nn.L1Loss, RGBBackgroundL1Loss
+    loss.py:388-400) in one pass: fake NHWC [N, H, W, C >= 3] bf16 / fp32 with RGB in channels 0..2 (`net_output.permute(0, 2, 3, 1)` is
+    zero-copy), real NCHW [N, 3, H, W], back fp32 [N, H, W] view (channel 0 of the one-hot label; None unless COLOR_BACKGROUND is set).
+    `flags`: COLOR_LAB | COLOR_RGB | COLOR_BACKGROUND; a term not selected is 0 and costs nothing.  Three fp32 scalars (views of one
+    tensor), gradient to `fake` only.  Two launches forward, one backward."""
+    flags = int(flags)
+    if not 1 <= flags <= 7:
+        raise ValueError("color_losses: flags must select at least one of COLOR_LAB, COLOR_RGB, COLOR_BACKGROUND")
+    if fake.dim() != 4 or real.dim() != 4 or real.shape[1] != 3 or fake.shape[-1] < 3 or \
+            (fake.shape[0], fake.shape[1], fake.shape[2]) != (real.shape[0], real.shape[2], real.shape[3]):
+        raise ValueError(f"color_losses: NHWC image {tuple(fake.shape)} does not match the NCHW target {tuple(real.shape)}")
+    real = real.detach()
+    if real.dtype != torch.float32:
+        real = real.float()
+    if not real.is_contiguous():
+        real = real.contiguous()
+    if flags & COLOR_BACKGROUND:
+        if back is None:
+            raise ValueError("color_losses: COLOR_BACKGROUND needs the background plane")
+        back = back.detach()
+        if back.dtype != torch.float32:
+            back = back.float()
+        if tuple(back.shape) != (fake.shape[0], fake.shape[1], fake.shape[2]):
+            raise ValueError(f"color_losses: background plane {tuple(back.shape)} does not match the image")
+        if back.stride(2) != 1 or back.stride(1) != back.shape[2]:
+            back = back.contiguous()
+    else:
+        back = None
+    return _ColorLossFn.apply(fake, real, back, flags)
+
+
 class _WeightedSumFn(torch.autograd.Function):
     """sum_k w_k * v_k of K scalar tensors as THREE launches forward (stack, mul, sum) and ONE backward (g * w), whatever K: the loss
     modules used to chain `total = total + val * w` -- 2 launches forward and 2 backward per term, ~100 five-microsecond
