@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MG_ABI_VERSION 7
+#define MG_ABI_VERSION 8
 
 enum { MG_F32 = 0, MG_BF16 = 1 };
 enum { MG_ACT_NONE = 0, MG_ACT_RELU = 1, MG_ACT_LRELU = 2, MG_ACT_TANH = 3 };
@@ -526,25 +526,42 @@ int mg_allreduce_grads(int64_t comm, float* bucket /* device, [n] fp32, in place
 int mg_probe_mfma_layout(float* out /* [3][64][16] */, void* stream);
 int mg_probe_tr16(const uint16_t* in /* [64][4] elements via LDS */, uint16_t* out /* [64][4] */, void* stream);
 
-/* Tuning switches for A/B measurements (value 0 / 1, all default 1): key 0 = conv pipeline (0 register-staged
- * double buffer, 1 LDS-DMA ring); 1 = allow 256x256 tiles; 2 = 3x3 halo-tile kernel; 3 = kernel-row 3x3 weight-
- * gradient kernel; 4 = 128-channel x 16x16-pixel halo tiles; 5 = split-K for low-resolution long-K convolutions;
- * 6 = kernels for convolutions over an 8-channel input, forward and weight gradient (0 none, 1 only the register-weight 3x3 / stride-1
- *     ones, 2 default: also the LDS-weight kernels for any window of at most 7x7 taps at stride 1 or 2);
- * 7 = bf16 conv epilogues exchange channel quads between the two half-waves (v_permlane32_swap) and store 16 bytes per lane;
- * 8 = wave-per-pixel dot-product kernel for convolutions with <= 4 output channels over >= 128 input channels (the discriminators' heads).
- * 9 = weight-slab ring depth of the big halo tile (3 default, or 4); 15 = 1: the SPADE halo kernel loads x in its epilogue instead of
- * ahead of its K loop (default 0); 17 = 1: two K slices also for 161..320-workgroup launches with >= 256 K steps (default 0);
- * 18 = stages a split of the generic weight-gradient kernel keeps at least (default 32); 22 = the register-resident-weights kernel for 3x3 convolutions
- * over exactly 64 input channels (mg_conv_halo64.hip; bitwise the results of the kernel it replaces); 24 = pixel width of the column stripes the
- * kernel-row 3x3 weight-gradient kernel walks inside an image (a multiple of 32; default 64; 0 = whole image rows in raster order).
- * Results agree within accumulation-order rounding whatever the setting (each setting is bit-reproducible except
- * the weight gradients, which use fp32 atomics).
- * MEASUREMENT builds (wrong or no results, timing only; tools/probe_halo.py, tools/probe_wgrad3x3.py): key 10 = 1..6 variants of the big
- * halo tile (K loop only / no weight stream / no barrier / per-tap stamps / per-phase stamps / stores off), 12 = 1 stamped build of the
- * 3x3 weight-gradient kernel, 13 and 14 = low and high half of the device address the stamps go to, 21 = bytes of extra dynamic LDS per
- * halo-conv workgroup (81920 leaves ONE resident per CU = one wave per SIMD: tools/gate1_lone_wave.py).  All default 0. */
+/* Tuning switches for A/B measurements, reference paths of the tests and race screens.  Results agree within
+ * accumulation-order rounding whatever the setting (each setting is bit-reproducible except the weight gradients,
+ * which use fp32 atomics).  The numbers are fixed: profiles and the design log refer to them, and a number that
+ * is missing (0, 9, 17: switches that are gone) is not reused.  Defaults and ranges live in csrc/mg_options.h.
+ * MG_OPT_PROBE_*: measurement builds only (-DMG_PROBES=1, tools/build_variant.py; wrong or no results, timing
+ * only); the product library refuses them. */
+enum mg_option {
+    MG_OPT_CONV_BIGTILES      = 1,   /* 0 / 1, default 1: allow the 128x256 / 256x256 tiles of the tap-list kernel */
+    MG_OPT_CONV_HALO          = 2,   /* 0 / 1, default 1: 3x3 stride-1 convolutions on the halo-tile kernels (mg_conv_halo.hip, mg_conv_halo64.hip); 0 = tap-list kernel */
+    MG_OPT_WGRAD3X3           = 3,   /* 0 / 1, default 1: kernel-row 3x3 weight-gradient kernel; 0 = always the generic tap-per-workgroup kernel */
+    MG_OPT_CONV_HALO_BIG      = 4,   /* 0 / 1, default 1: 128-channel x 16x16-pixel halo tiles where the launch is big enough */
+    MG_OPT_CONV_SPLITK        = 5,   /* 0 / 1, default 1: deterministic split-K for low-resolution long-K convolutions */
+    MG_OPT_CONV_THIN          = 6,   /* 0..2, default 2: kernels for convolutions over an 8-channel input, forward and weight gradient: 0 none, 1 only the
+                                        register-weight 3x3 / stride-1 ones, 2 also the LDS-weight kernels for any window of at most 7x7 taps at stride 1 or 2 */
+    MG_OPT_CONV_WIDE          = 7,   /* 0 / 1, default 1: bf16 conv epilogues exchange channel quads between the two half-waves (v_permlane32_swap) and store 16 bytes per lane */
+    MG_OPT_CONV_DOT           = 8,   /* 0..2, default 2: few-output-channel convolutions (the discriminators' heads): 0 tap-list kernel, 1 only the wave-per-pixel
+                                        dot-product kernel (<= 4 output channels over >= 128 input channels), 2 also the <= 16-row kernel over 64 input channels */
+    MG_OPT_PROBE_HALO_VARIANT = 10,  /* 0..6, default 0: variants of the big halo tile: 1 K loop only, 2 no weight stream, 3 no barrier, 4 per-tap stamps,
+                                        5 per-phase stamps, 6 the same with stores off (tools/probe_halo.py) */
+    MG_OPT_PROBE_WGRAD3X3     = 12,  /* 0 / 1, default 0: stamped build of the 3x3 weight-gradient kernel (tools/probe_wgrad3x3.py) */
+    MG_OPT_PROBE_ADDR_LO      = 13,  /* any int32, default 0: low half of the device address the stamps go to; takes effect when the high half is set */
+    MG_OPT_PROBE_ADDR_HI      = 14,  /* any int32, default 0: high half of that address; setting it hands the address to the stamped kernels */
+    MG_OPT_PROBE_NOXPRE       = 15,  /* 0 / 1, default 0: the SPADE halo kernel loads x in its epilogue instead of ahead of its K loop */
+    MG_OPT_WGRAD_MIN_STAGES   = 18,  /* 1..1024, default 32: stages (of 32 / 16 pixels) a split of the generic weight-gradient kernel keeps at least */
+    MG_OPT_NORM_BWD_VEC       = 19,  /* 0 / 1, default 1: 16-byte norm backward reduction; 0 = the 8-byte quad kernel */
+    MG_OPT_PROBE_HALO_LDSPAD  = 21,  /* 0..81920, default 0: bytes of extra dynamic LDS per halo-conv workgroup (81920 leaves one resident per CU: tools/gate1_lone_wave.py) */
+    MG_OPT_CONV_HALO64        = 22,  /* 0 / 1, default 1: register-resident-weights kernel for 3x3 convolutions over exactly 64 input channels (mg_conv_halo64.hip);
+                                        0 = the halo kernel it replaces, bitwise the same results */
+    MG_OPT_PROBE_HALO64_DBG   = 23,  /* 0..7 (bits), default 0: mg_conv_halo64 with 1 no stores, 2 no patch DMA after the first tile, 4 no K loop (tools/dbg_halo64.py) */
+    MG_OPT_WGRAD3X3_STRIPE    = 24,  /* 0..4096 in steps of 32, default 64: pixel width of the column stripes the kernel-row 3x3 weight-gradient kernel walks
+                                        inside an image; 0 = whole image rows in raster order */
+    MG_OPT_END
+};
+/* MG_ERR_ARG ("unknown key/value") for a key that does not exist in this build or a value outside its range. */
 int         mg_set_option(int32_t key, int32_t value);
+int         mg_get_option(int32_t key, int32_t* value);
 
 /* sizeof(mg_conv_desc) (which=0) / sizeof(mg_wgrad_desc) (which=1): lets a
  * foreign-language binding check its struct mirror without a GPU. */

@@ -8,6 +8,7 @@ the contract emulator that lives under ``oracle/`` -- product code never does.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -15,8 +16,13 @@ MG_F32, MG_BF16 = 0, 1
 MG_ACT_NONE, MG_ACT_RELU, MG_ACT_LRELU, MG_ACT_TANH = 0, 1, 2, 3
 MG_EPI_PLAIN, MG_EPI_SPADE = 0, 1
 MG_MAX_TAPS = 64
-MG_ABI_VERSION = 7
+MG_ABI_VERSION = 8
 MG_COMM_ID_BYTES = 128
+
+# enum mg_option (include/michigan_hip.h): the tuning switches of mg_set_option / mg_get_option; OPT_PROBE_* exist in -DMG_PROBES=1 builds only
+OPT_CONV_BIGTILES, OPT_CONV_HALO, OPT_WGRAD3X3, OPT_CONV_HALO_BIG, OPT_CONV_SPLITK, OPT_CONV_THIN, OPT_CONV_WIDE, OPT_CONV_DOT = 1, 2, 3, 4, 5, 6, 7, 8
+OPT_PROBE_HALO_VARIANT, OPT_PROBE_WGRAD3X3, OPT_PROBE_ADDR_LO, OPT_PROBE_ADDR_HI, OPT_PROBE_NOXPRE = 10, 12, 13, 14, 15
+OPT_WGRAD_MIN_STAGES, OPT_NORM_BWD_VEC, OPT_PROBE_HALO_LDSPAD, OPT_CONV_HALO64, OPT_PROBE_HALO64_DBG, OPT_WGRAD3X3_STRIPE = 18, 19, 21, 22, 23, 24
 
 _i32, _f32, _vp, _i64 = ctypes.c_int32, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64
 
@@ -165,6 +171,7 @@ _PROTOS = {
     "mg_probe_mfma_layout": ([_vp, _vp], _i32),
     "mg_probe_tr16": ([_vp, _vp, _vp], _i32),
     "mg_set_option": ([_i32, _i32], _i32),
+    "mg_get_option": ([_i32, ctypes.POINTER(_i32)], _i32),
     "mg_sizeof_desc": ([_i32], _i32),
     "mg_abi_version": ([], _i32),
     "mg_last_error": ([], ctypes.c_char_p),
@@ -242,3 +249,25 @@ def set_backend(obj):
     global _backend
     prev, _backend = _backend, obj
     return prev
+
+
+def get_option(key, be=None):
+    """Current value of a tuning switch (OPT_*)."""
+    v = _i32()
+    (be or backend()).mg_get_option(key, ctypes.byref(v))
+    return v.value
+
+
+@contextlib.contextmanager
+def options(values, be=None):
+    """``with options({OPT_CONV_THIN: 0}): ...`` -- set tuning switches for a scope; on exit, also when the body raises, every
+    one is put back to the value it had on entry (read with mg_get_option, not remembered defaults)."""
+    be = be or backend()
+    saved = {key: get_option(key, be) for key in values}
+    try:
+        for key, v in values.items():
+            be.mg_set_option(key, v)
+        yield
+    finally:
+        for key, v in saved.items():
+            be.mg_set_option(key, v)

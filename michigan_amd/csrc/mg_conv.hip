@@ -15,30 +15,7 @@
 // pipe).  bf16 uses v_mfma_f32_32x32x16_bf16, f32 uses v_mfma_f32_32x32x2_f32
 // (exact fp32 fma; two-level sums, mma_f32_chunk) -- same tiling, same LDS image (64 B of K per row).
 
-int g_mg_conv_splitk_wide = 0;   // ... also for launches of 161..320 workgroups with >= 256 K steps (mg_set_option(17, 1)): measured flat, off
-int g_mg_conv_splitk = 1;        // deterministic split-K for low-resolution long-K layers (mg_set_option(5, v))
-int g_mg_conv_halo_big = 1;      // 128 channels x 16x16 pixel halo tiles where the launch is big enough (mg_set_option(4, v))
-int g_mg_conv_halo = 1;          // 3x3 stride-1 convs on the LDS halo-tile kernel (mg_set_option(2, v))
-int g_mg_conv_bigtiles = 1;      // allow the 128x256 / 256x256 tiles (mg_set_option(1, v))
-extern int g_mg_wgrad3x3;          // mg_wgrad.hip (mg_set_option(3, v))
-extern int g_mg_norm_bwd_vec;      // mg_norm.hip (mg_set_option(19, v))
-extern int g_mg_wgrad_min_stages;  // mg_wgrad.hip (mg_set_option(18, v))
-extern int g_mg_conv_thin;         // mg_conv_thin.hip (mg_set_option(6, v))
-extern int g_mg_conv_dot;          // mg_conv_dot.hip (mg_set_option(8, v))
-extern int g_mg_wgrad3x3_stripe;   // mg_wgrad3x3.hip (mg_set_option(24, v))
-extern int g_mg_conv_halo64;       // mg_conv_halo64.hip (mg_set_option(22, v))
-extern int g_mg_conv_halo64_dbg;   // mg_conv_halo64.hip (mg_set_option(23, bits)): measurement only
-int g_mg_conv_noxpre = 0;        // mg_set_option(15, 1): A/B switch, the SPADE halo kernel loads x in its epilogue instead of ahead of the main loop
-int g_mg_conv_halo_ldspad = 0;  // MEASUREMENT ONLY (mg_set_option(21, bytes), MG_PROBES builds): extra dynamic LDS per halo workgroup -> fewer residents per CU
-int g_mg_conv_dbg_noepi = 0;     // MEASUREMENT ONLY (mg_set_option(10, 1)): the halo kernel returns before its epilogue -- wrong results, main-loop time
-int g_mg_conv_wide = 1;          // bf16 epilogues store 16 bytes per lane after a half-wave quad exchange (mg_set_option(7, v))
-int g_mg_conv_pipeline = 1;      // 0 = register-staged double buffer, 1 = LDS-DMA 3-stage ring (mg_set_option(0, v))
-
 #include "mg_conv_common.h"
-int conv_halo_set_probe(unsigned long long addr);
-int wgrad3x3_set_probe(unsigned long long addr);         // mg_wgrad3x3.hip (measurement build)
-int g_mg_wgrad3x3_probe = 0;       // mg_set_option(12, 1): stamped build of wgrad3x3_kernel<2, 2>          // mg_conv_halo.hip (measurement builds)
-static unsigned g_probe_lo = 0;
 #include <map>
 #include <mutex>
 
@@ -438,53 +415,49 @@ int launch_conv_p(ConvK& k, hipStream_t st)
         return mg_fail(MG_ERR_ARG, "mg_conv_taps: CoutP=%d too small for Cout_gemm=%d (tile %d)", k.CoutP, k.Cout_gemm, TM);
     const long nblk = (long)k.tiles_m * tiles_n;
     if (nblk <= 0 || nblk > 0x7fffffffL) return mg_fail(MG_ERR_ARG, "mg_conv_taps: bad grid %ld", nblk);
-    if constexpr (TM % (16 * WM * WN) == 0) {
-        if (g_mg_conv_pipeline == 1 || WM * WN != 4 || MT * NT > 4) {
-            const size_t stage = (size_t)(TM + TN) * ROWB;
-            const size_t ldsr = (stage >= 32768 ? 4 : 3) * stage + 2 * TM * sizeof(float);
-            auto kern = conv_taps_glds_kernel<T, WM, WN, MT, NT, EPI, PACK>;
-            k.ntiles = (int)nblk; k.ksplit = 1; k.ws = nullptr;
-            // Low-resolution layers with a long K loop (1024-channel blocks at the 8x8..32x32 latents, the gamma/beta
-            // dgrads there): a few dozen workgroups each pull hundreds of K steps through ONE CU's L2->LDS path
-            // (~50 GB/s per CU, 0.33 us per step whatever the tile, ring depth or wave count) while most CUs idle.
-            // Split K across workgroups: every slice stores its fp32 partial tile, a finishing pass adds the slices
-            // in a fixed order (deterministic) and applies bias / residual / activation.
-            if constexpr (EPI == MG_EPI_PLAIN && !PACK && WM == 2 && WN == 2 && MT == 2 && NT == 2) {
-                const int nchunk = (k.Cin * (int)sizeof(T) + ROWB - 1) / ROWB, nkk = k.ntaps * nchunk;
-                // (mg_set_option(17, 1) widens the rule to 161..320 workgroups with >= 256 K steps -- the 18432-deep gamma|beta data gradient at
-                // 64x64 runs 256 workgroups, one per CU, at 760 TFLOP/s; two slices per tile measured 69.35 vs 69.31 ms per step: flat, left off)
-                if (g_mg_conv_splitk && (nblk <= 160 || (nblk <= 320 && nkk >= 256 && g_mg_conv_splitk_wide)) && nkk >= 64 && (k.Cout & 3) == 0 && (k.Cout_gemm & 3) == 0) {
-                    int S = (int)(((nblk <= 160 ? 384 : 512) + nblk - 1) / nblk);
-                    if (S > nkk / 16) S = nkk / 16;
-                    if (S > 16) S = 16;
-                    if (S >= 2) {
-                        k.ws = splitk_workspace(st, (size_t)S * k.ngemm * k.Cout_gemm * sizeof(float));
-                        if (k.ws == nullptr) return mg_fail(MG_ERR_LAUNCH, "mg_conv_taps: split-K scratch allocation failed");
-                        k.ksplit = S;
-                        hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * S)), dim3(64 * WM * WN), ldsr, st, k);
-                        const long nel = (long)k.ngemm * (k.Cout / 4);
-                        const long fb = (nel + 255) / 256;
-                        hipLaunchKernelGGL(conv_splitk_finish<T>, dim3((unsigned)(fb > 2048 ? 2048 : fb)), dim3(256), 0, st, k);
-                        MG_CHECK_LAUNCH("mg_conv_taps(glds, split-K)");
-                        return MG_OK;
-                    }
+    if constexpr (TM % (16 * WM * WN) == 0) {                                        // the LDS-DMA ring: every tile but the 32-row one
+        const size_t stage = (size_t)(TM + TN) * ROWB;
+        const size_t ldsr = (stage >= 32768 ? 4 : 3) * stage + 2 * TM * sizeof(float);
+        auto kern = conv_taps_glds_kernel<T, WM, WN, MT, NT, EPI, PACK>;
+        k.ntiles = (int)nblk; k.ksplit = 1; k.ws = nullptr;
+        // Low-resolution layers with a long K loop (1024-channel blocks at the 8x8..32x32 latents, the gamma/beta
+        // dgrads there): a few dozen workgroups each pull hundreds of K steps through ONE CU's L2->LDS path
+        // (~50 GB/s per CU, 0.33 us per step whatever the tile, ring depth or wave count) while most CUs idle.
+        // Split K across workgroups: every slice stores its fp32 partial tile, a finishing pass adds the slices
+        // in a fixed order (deterministic) and applies bias / residual / activation.
+        if constexpr (EPI == MG_EPI_PLAIN && !PACK && WM == 2 && WN == 2 && MT == 2 && NT == 2) {
+            const int nchunk = (k.Cin * (int)sizeof(T) + ROWB - 1) / ROWB, nkk = k.ntaps * nchunk;
+            // (widening the rule to 161..320 workgroups with >= 256 K steps -- the 18432-deep gamma|beta data gradient at 64x64 runs 256
+            // workgroups, one per CU, at 760 TFLOP/s -- measured flat, 69.35 vs 69.31 ms per step, and was removed)
+            if (mg_opt(MG_OPT_CONV_SPLITK) && nblk <= 160 && nkk >= 64 && (k.Cout & 3) == 0 && (k.Cout_gemm & 3) == 0) {
+                int S = (int)((384 + nblk - 1) / nblk);
+                if (S > nkk / 16) S = nkk / 16;
+                if (S > 16) S = 16;
+                if (S >= 2) {
+                    k.ws = splitk_workspace(st, (size_t)S * k.ngemm * k.Cout_gemm * sizeof(float));
+                    if (k.ws == nullptr) return mg_fail(MG_ERR_LAUNCH, "mg_conv_taps: split-K scratch allocation failed");
+                    k.ksplit = S;
+                    hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * S)), dim3(64 * WM * WN), ldsr, st, k);
+                    const long nel = (long)k.ngemm * (k.Cout / 4);
+                    const long fb = (nel + 255) / 256;
+                    hipLaunchKernelGGL(conv_splitk_finish<T>, dim3((unsigned)(fb > 2048 ? 2048 : fb)), dim3(256), 0, st, k);
+                    MG_CHECK_LAUNCH("mg_conv_taps(glds, split-K)");
+                    return MG_OK;
                 }
             }
-            if (ldsr > 65536) {
-                mg_raise_lds_cap(reinterpret_cast<const void*>(kern), (int)ldsr);       // once per instantiation and device
-            }
-            hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * WM * WN), ldsr, st, k);
-            MG_CHECK_LAUNCH("mg_conv_taps(glds)");
-            return MG_OK;
         }
-    }
-    if constexpr (WM * WN != 4 || MT * NT > 4) return mg_fail(MG_ERR_UNSUPPORTED, "mg_conv_taps: large tiles need the LDS-DMA pipeline");
-    const size_t lds = 2 * (size_t)(TM + TN) * ROWB + 2 * TM * sizeof(float);
-    if constexpr (WM * WN == 4 && MT * NT <= 4) {
+        if (ldsr > 65536) {
+            mg_raise_lds_cap(reinterpret_cast<const void*>(kern), (int)ldsr);       // once per instantiation and device
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * WM * WN), ldsr, st, k);
+        MG_CHECK_LAUNCH("mg_conv_taps(glds)");
+        return MG_OK;
+    } else {                                                                          // <1, 4, 1, 2>: register-staged double buffer
+        const size_t lds = 2 * (size_t)(TM + TN) * ROWB + 2 * TM * sizeof(float);
         hipLaunchKernelGGL((conv_taps_kernel<T, WM, WN, MT, NT, EPI, PACK>), dim3((unsigned)nblk), dim3(NTHR), lds, st, k);
         MG_CHECK_LAUNCH("mg_conv_taps");
+        return MG_OK;
     }
-    return MG_OK;
 }
 
 template <typename T, int EPI>
@@ -493,7 +466,7 @@ int dispatch_tiles(ConvK& k, hipStream_t st)
     // Largest tile that still yields >= 1.5 workgroups per CU (256 CUs); big tiles halve the bytes
     // staged per FLOP, small ones keep low-resolution layers from under-filling the chip.
     auto wgs = [&](int tm, int tn) { return (long)((k.Cout_gemm + tm - 1) / tm) * ((k.ngemm + tn - 1) / tn); };
-    const bool big = g_mg_conv_pipeline == 1 && g_mg_conv_bigtiles;
+    const bool big = mg_opt(MG_OPT_CONV_BIGTILES);
     // 256x256 (one 8-wave workgroup per CU) only pays when the K loop is long enough to amortise its
     // exposed prologue/epilogue: measured +10..14 % at K >= 4608, -5..-13 % at K = 1152 (SPADE convs).
     const int kchunks = k.ntaps * ((k.Cin * (int)sizeof(T) + ROWB - 1) / ROWB);
@@ -510,7 +483,7 @@ template <typename T>
 bool halo_applies(const ConvK& k)
 {
     constexpr int CH = ROWB / (int)sizeof(T);
-    if (!g_mg_conv_halo || g_mg_conv_pipeline != 1) return false;
+    if (!mg_opt(MG_OPT_CONV_HALO)) return false;
     if (k.ntaps != 9 || k.isy != 1 || k.isx != 1 || k.osy != 1 || k.osx != 1 || k.ooy != 0 || k.oox != 0) return false;
     if (k.Hj != k.Hin || k.Wj != k.Win || k.Hout != k.Hin || k.Wout != k.Win) return false;
     if (k.Cin % CH || k.Cout_gemm <= 32 || k.Hin < 8 || k.Win < 16) return false;
@@ -580,39 +553,10 @@ extern "C" int mg_conv_taps(const mg_conv_desc* d, void* stream)
     k.mslope = d->mask_slope;
     k.ngemm = d->N * d->Hj * d->Wj; k.tiles_m = 0; k.tpc = 1; k.tiles_y = k.tiles_x = 0;
     k.ksplit = 1; k.ntiles = 1; k.ws = nullptr;
-    k.wide = ((g_mg_conv_wide && d->dtype == MG_BF16 && (d->Cout % 8) == 0) ? 1 : 0) | (g_mg_conv_dbg_noepi ? 2 : 0) | (g_mg_conv_dbg_noepi == 6 ? 4 : 0) | (g_mg_conv_noxpre ? 8 : 0);
+    const int probe = mg_opt(MG_OPT_PROBE_HALO_VARIANT);
+    k.wide = ((mg_opt(MG_OPT_CONV_WIDE) && d->dtype == MG_BF16 && (d->Cout % 8) == 0) ? 1 : 0) | (probe ? 2 : 0) | (probe == 6 ? 4 : 0) | (mg_opt(MG_OPT_PROBE_NOXPRE) ? 8 : 0);
     for (int t = 0; t < MG_MAX_TAPS; ++t)
         k.tap[t] = t < d->ntaps ? (int)((((uint32_t)(int)d->tap_dy[t]) & 0xffffu) | (((uint32_t)(int)d->tap_dx[t]) << 16)) : 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return d->dtype == MG_BF16 ? dispatch_conv<uint16_t>(k, d->epilogue, st) : dispatch_conv<float>(k, d->epilogue, st);
-}
-
-extern "C" int mg_set_option(int32_t key, int32_t value)
-{
-    if (key == 0 && (value == 0 || value == 1)) { g_mg_conv_pipeline = value; return MG_OK; }
-    if (key == 1 && (value == 0 || value == 1)) { g_mg_conv_bigtiles = value; return MG_OK; }
-    if (key == 2 && (value == 0 || value == 1)) { g_mg_conv_halo = value; return MG_OK; }
-    if (key == 3 && (value == 0 || value == 1)) { g_mg_wgrad3x3 = value; return MG_OK; }
-    if (key == 4 && (value == 0 || value == 1)) { g_mg_conv_halo_big = value; return MG_OK; }
-    if (key == 5 && (value == 0 || value == 1)) { g_mg_conv_splitk = value; return MG_OK; }
-    if (key == 17 && (value == 0 || value == 1)) { g_mg_conv_splitk_wide = value; return MG_OK; }
-    if (key == 6 && value >= 0 && value <= 2) { g_mg_conv_thin = value; return MG_OK; }
-    if (key == 18 && value >= 1 && value <= 1024) { g_mg_wgrad_min_stages = value; return MG_OK; }
-    if (key == 19 && (value == 0 || value == 1)) { g_mg_norm_bwd_vec = value; return MG_OK; }
-    if (key == 7 && (value == 0 || value == 1)) { g_mg_conv_wide = value; return MG_OK; }
-    if (key == 8 && value >= 0 && value <= 2) { g_mg_conv_dot = value; return MG_OK; }
-#if MG_PROBES
-    // measurement builds only (python tools/build_variant.py probes mg_conv.hip mg_conv_halo.hip mg_wgrad3x3.hip -DMG_PROBES=1): truncated /
-    // stamped variants of the big halo tile and of wgrad3x3_kernel, their stamp buffer, the SPADE x prefetch off
-    if (key == 15 && (value == 0 || value == 1)) { g_mg_conv_noxpre = value; return MG_OK; }
-    if (key == 13) { g_probe_lo = (unsigned)value; return MG_OK; }
-    if (key == 14) { const unsigned long long a = ((unsigned long long)(unsigned)value << 32) | g_probe_lo; const int r = conv_halo_set_probe(a); return r != MG_OK ? r : wgrad3x3_set_probe(a); }
-    if (key == 12 && (value == 0 || value == 1)) { g_mg_wgrad3x3_probe = value; return MG_OK; }
-    if (key == 10 && value >= 0 && value <= 6) { g_mg_conv_dbg_noepi = value; return MG_OK; }
-    if (key == 21 && value >= 0 && value <= 80 * 1024) { g_mg_conv_halo_ldspad = value; return MG_OK; }
-#endif
-    if (key == 22 && (value == 0 || value == 1)) { g_mg_conv_halo64 = value; return MG_OK; }
-    if (key == 23 && value >= 0 && value <= 7) { g_mg_conv_halo64_dbg = value; return MG_OK; }
-    if (key == 24 && value >= 0 && value <= 4096 && (value % 32) == 0) { g_mg_wgrad3x3_stripe = value; return MG_OK; }
-    return mg_fail(MG_ERR_ARG, "mg_set_option: unknown key/value %d/%d", key, value);
 }

@@ -10,7 +10,6 @@
 // rounding to the storage type.
 #include "mg_conv_common.h"
 
-int g_mg_conv_dot = 2;             // mg_set_option(8, v): 0 = few-output-channel convs stay on the tap-list kernel, 1 = only the wave-per-pixel dot kernel
 
 namespace {
 
@@ -237,7 +236,7 @@ bool fewout_geom(const ConvK& k, FewGeom& g)
 
 bool conv_dot_applies(const ConvK& k, int dtype, int epilogue)
 {
-    if (!g_mg_conv_dot || epilogue != MG_EPI_PLAIN) return false;
+    if (!mg_opt(MG_OPT_CONV_DOT) || epilogue != MG_EPI_PLAIN) return false;
     const int esz = dtype == MG_BF16 ? 2 : 4;
     if (k.Cout < 1 || k.Cout > DOT_MAXCO || k.Cout_gemm > 32) return false;
     if (k.Cin < 128 || (k.Cin * esz) % 16 != 0) return false;                 // short reductions stay on the packed-taps MFMA path
@@ -260,7 +259,7 @@ int launch_conv_dot(ConvK& k, int dtype, hipStream_t st)
 // bf16, 64 input channels, at most 16 GEMM rows, at most 9 taps inside a 3x3 window at input stride 1, any output stride / offset
 bool conv_fewout_applies(const ConvK& k, int dtype, int epilogue)
 {
-    if (g_mg_conv_dot < 2 || dtype != MG_BF16 || epilogue != MG_EPI_PLAIN) return false;
+    if (mg_opt(MG_OPT_CONV_DOT) < 2 || dtype != MG_BF16 || epilogue != MG_EPI_PLAIN) return false;
     if (k.Cin != 64 || k.Cout_gemm > 16 || k.ntaps > FEW_MAXT || k.isy != 1 || k.isx != 1) return false;
     if (k.resid || k.x) return false;
     FewGeom g;

@@ -31,9 +31,6 @@
 #define MG_HALO_SCHED 0          // scheduling-hint experiments (tools/ab_halo_sched.sh); 0 = compiler's own schedule
 #endif
 
-extern int g_mg_conv_halo_big;     // mg_set_option(4, v): 0 = never use the 128 x 16x16 geometry
-extern int g_mg_conv_dbg_noepi;    // mg_set_option(10, v): 0 product; 1 main loop only; 2..4 probes of the big tile (below)
-extern int g_mg_conv_halo_ldspad;  // mg_set_option(21, bytes), MG_PROBES builds: pad the dynamic LDS request (one resident per CU = one wave per SIMD)
 
 namespace {
 
@@ -58,13 +55,9 @@ template <int WM, int NT> struct HaloGeom {
     static constexpr int OCC = NT == 4 ? 2 : 3;                 // waves per SIMD the register budget is set for
 };
 
-#ifndef MG_PROBES
-#define MG_PROBES 0              // 1: also build the stamped / truncated measurement variants of the big tile (tools/probe_halo.py via tools/build_variant.py)
-#endif
-
-// PROBE (measurement builds of the big tile, mg_set_option(10, 2..4); results are WRONG, only the time / the stamps mean anything):
+// PROBE (measurement builds of the big tile, MG_OPT_PROBE_HALO_VARIANT = 2..4; results are WRONG, only the time / the stamps mean anything):
 //   1 = no weight stream after the prologue, 2 = no s_barrier, 3 = s_memtime stamps around the wait, the barrier and the tap
-__device__ unsigned long long* g_mg_probe_out = nullptr;     // PROBE 4: [workgroup][wave][4] stamps (mg_set_option(13 / 14, low / high half of a device address))
+__device__ unsigned long long* g_mg_probe_out = nullptr;     // PROBE 4: [workgroup][wave][4] stamps (MG_OPT_PROBE_ADDR_LO / _HI: low / high half of a device address)
 
 __device__ __forceinline__ unsigned long long stamp()
 {
@@ -260,7 +253,7 @@ __global__ __launch_bounds__(NTHR, (NT == 4 || sizeof(T) == 4 ? 2 : 3)) void con
     uint2 xpre[2 * NT * 2] = {};
     bool xpre_ok = false;
     if constexpr (XPRE) {
-        xpre_ok = ((d.Cout | d.Cout_gemm) & 3) == 0 && d.act != MG_ACT_TANH && !(d.wide & 8);          // the batched epilogue will run (bit 3: A/B switch, mg_set_option(15, 1))
+        xpre_ok = ((d.Cout | d.Cout_gemm) & 3) == 0 && d.act != MG_ACT_TANH && !(d.wide & 8);          // the batched epilogue will run (bit 3: A/B switch, MG_OPT_PROBE_NOXPRE)
         if (xpre_ok) {
             const uint16_t* __restrict__ X = reinterpret_cast<const uint16_t*>(d.x);
 #pragma unroll
@@ -362,7 +355,7 @@ __global__ __launch_bounds__(NTHR, (NT == 4 || sizeof(T) == 4 ? 2 : 3)) void con
     }
 
 #if MG_PROBES
-    if (PROBE != 4 && (d.wide & 2)) {                            // measurement aid (mg_set_option(10, 1)): main loop only; one store keeps the MFMAs alive
+    if (PROBE != 4 && (d.wide & 2)) {                            // measurement aid (MG_OPT_PROBE_HALO_VARIANT = 1): main loop only; one store keeps the MFMAs alive
         if (acc[0][0][0] == 12345.678f) reinterpret_cast<T*>(d.out)[0] = (T)1;
         return;
     }
@@ -399,7 +392,7 @@ int launch_halo_g(ConvK& k, hipStream_t st)
     auto kern = conv3x3_halo_kernel<T, EPI, WM, NT, PROBE>;
     int lds = G::LDS;
 #if MG_PROBES
-    lds += g_mg_conv_halo_ldspad;
+    lds += mg_opt(MG_OPT_PROBE_HALO_LDSPAD);
 #endif
     if (lds > 65536) {
         mg_raise_lds_cap(reinterpret_cast<const void*>(kern), lds);
@@ -419,15 +412,16 @@ int launch_halo(ConvK& k, hipStream_t st)
     else {
     // 16x16-pixel tiles once they still give every CU its two workgroups at least twice over
     const long big = (long)k.N * ((k.Hin + 15) / 16) * ((k.Win + 15) / 16) * ((k.Cout_gemm + 127) / 128);
-    if (g_mg_conv_halo_big && k.Hin >= 16 && big >= 1024) {
+    if (mg_opt(MG_OPT_CONV_HALO_BIG) && k.Hin >= 16 && big >= 1024) {
 #if MG_PROBES
         if constexpr (sizeof(T) == 2) {
+            const int probe = mg_opt(MG_OPT_PROBE_HALO_VARIANT);
             if constexpr (EPI == MG_EPI_PLAIN) {
-                if (g_mg_conv_dbg_noepi == 2) return launch_halo_g<T, EPI, 2, 4, 1>(k, st);
-                if (g_mg_conv_dbg_noepi == 3) return launch_halo_g<T, EPI, 2, 4, 2>(k, st);
-                if (g_mg_conv_dbg_noepi == 4) return launch_halo_g<T, EPI, 2, 4, 3>(k, st);
+                if (probe == 2) return launch_halo_g<T, EPI, 2, 4, 1>(k, st);
+                if (probe == 3) return launch_halo_g<T, EPI, 2, 4, 2>(k, st);
+                if (probe == 4) return launch_halo_g<T, EPI, 2, 4, 3>(k, st);
             }
-            if (g_mg_conv_dbg_noepi >= 5) return launch_halo_g<T, EPI, 2, 4, 4>(k, st);      // 6: ... with the stores predicated off
+            if (probe >= 5) return launch_halo_g<T, EPI, 2, 4, 4>(k, st);      // 6: ... with the stores predicated off
         }
 #endif
         return launch_halo_g<T, EPI, 2, 4>(k, st);

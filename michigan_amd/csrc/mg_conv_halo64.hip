@@ -27,11 +27,8 @@
 //
 // Same K order as the shipped kernel (64-byte chunk -> tap -> 16-channel K step), so the outputs are BITWISE those of
 // conv3x3_halo_kernel<bf16, PLAIN, 1, 2> (tests/test_gpu_kernels.py::test_halo64_matches_the_shipped_halo_kernel_bitwise).
-// mg_set_option(22, 0) sends these launches back to it.
+// MG_OPT_CONV_HALO64 = 0 sends these launches back to it.
 #include "mg_conv_common.h"
-
-int g_mg_conv_halo64 = 1;          // mg_set_option(22, v)
-int g_mg_conv_halo64_dbg = 0;      // MEASUREMENT ONLY (mg_set_option(23, bits), wrong results): 1 = no stores, 2 = no patch DMA after the first tile, 4 = no K loop
 
 namespace {
 
@@ -58,7 +55,7 @@ struct Halo64Args {
     int nseg;               // x segments per strip
     int tiles_per_seg;      // 16x16 tiles a workgroup walks
     int bands;              // H / 16
-    int dbg;                // measurement bits (g_mg_conv_halo64_dbg)
+    int dbg;                // measurement bits (MG_OPT_PROBE_HALO64_DBG)
 };
 
 template <int ACT, int AUX>   // ACT: 0 none, 1 relu, 2 lrelu (0 <= slope <= 1).  AUX: 0 none, 1 residual add, 2 data-gradient mask
@@ -277,7 +274,7 @@ int act_kind(const ConvK& k) { return (k.act == MG_ACT_LRELU && !(k.slope >= 0.f
 // one of the lean epilogue cases of conv_epilogue_fast ({no aux} x {none, relu, lrelu}, {residual | mask} x {none}), 16-byte stores on
 bool conv_halo64_applies(const ConvK& k, int dtype, int epilogue)
 {
-    if (!g_mg_conv_halo64 || dtype != MG_BF16 || epilogue != MG_EPI_PLAIN) return false;
+    if (!mg_opt(MG_OPT_CONV_HALO) || !mg_opt(MG_OPT_CONV_HALO64) || dtype != MG_BF16 || epilogue != MG_EPI_PLAIN) return false;
     if (k.Cin != 64 || k.Cout != k.Cout_gemm || (k.Cout % 64) != 0 || k.CoutP < k.Cout) return false;
     if (k.ntaps != 9 || k.isy != 1 || k.isx != 1 || k.osy != 1 || k.osx != 1 || k.ooy != 0 || k.oox != 0) return false;
     if (k.Hj != k.Hin || k.Wj != k.Win || k.Hout != k.Hin || k.Wout != k.Win) return false;
@@ -310,7 +307,7 @@ int launch_conv_halo64(ConvK& k, hipStream_t st)
     g.nseg = nseg;
     g.tiles_per_seg = tiles_x / nseg;
     g.units = (int)(strips * nseg);
-    g.dbg = g_mg_conv_halo64_dbg;
+    g.dbg = mg_opt(MG_OPT_PROBE_HALO64_DBG);
     const int ak = aux_kind(k), ck = act_kind(k);
     if (ak == 1) return launch64<0, 1>(k, g, st);
     if (ak == 2) return launch64<0, 2>(k, g, st);

@@ -19,7 +19,6 @@
 #include "mg_conv_common.h"
 #include "mg_wgrad_common.h"
 
-int g_mg_conv_thin = 2;            // mg_set_option(6, v): 0 = 8-channel convs stay on the tap-list kernel, 1 = only the 3x3 / stride-1 ones leave it
 
 namespace {
 
@@ -625,7 +624,7 @@ int launch_wthin(Wg3K& k, hipStream_t st, int* nsplit, bool dry)
 // bf16, Cin == 8, the nine 3x3 taps at stride 1 onto a same-size output, plain epilogue without residual / mask / tanh
 bool conv_thin_applies(const ConvK& k, int dtype, int epilogue)
 {
-    if (!g_mg_conv_thin || dtype != MG_BF16 || epilogue != MG_EPI_PLAIN) return false;
+    if (!mg_opt(MG_OPT_CONV_THIN) || dtype != MG_BF16 || epilogue != MG_EPI_PLAIN) return false;
     if (k.Cin != 8 || k.ntaps != 9 || k.isy != 1 || k.isx != 1 || k.osy != 1 || k.osx != 1 || k.ooy != 0 || k.oox != 0) return false;
     if (k.Hj != k.Hin || k.Wj != k.Win || k.Hout != k.Hin || k.Wout != k.Win) return false;
     if (k.resid || k.x || k.act == MG_ACT_TANH) return false;
@@ -643,7 +642,7 @@ bool conv_thin_applies(const ConvK& k, int dtype, int epilogue)
 // bf16, Cin == 8, any window of at most 7 x 7 taps at stride 1 or 2 onto the whole output grid (osy = osx = 1), plain epilogue
 bool conv_thin_taps_applies(const ConvK& k, int dtype, int epilogue)
 {
-    if (g_mg_conv_thin < 2 || dtype != MG_BF16 || epilogue != MG_EPI_PLAIN) return false;
+    if (mg_opt(MG_OPT_CONV_THIN) < 2 || dtype != MG_BF16 || epilogue != MG_EPI_PLAIN) return false;
     if (k.Cin != 8 || k.osy != 1 || k.osx != 1 || k.ooy != 0 || k.oox != 0 || k.Hout != k.Hj || k.Wout != k.Wj) return false;
     if (k.resid || k.x || k.act == MG_ACT_TANH || (k.Cout & 7) || k.Cout_gemm > 128 || k.Cout_gemm < 32) return false;
     ThinTapsGeom g;
@@ -668,7 +667,7 @@ int launch_conv_thin(ConvK& k, hipStream_t st)
 // in raster order, stride 1, same-size dY.
 bool wgrad_thin_applies(const Wg3K& k)
 {
-    return g_mg_conv_thin && k.Cin == 8 && (k.Cg == 64 || k.Cg == 128) && (k.W % THIN_TW) == 0 &&
+    return mg_opt(MG_OPT_CONV_THIN) && k.Cin == 8 && (k.Cg == 64 || k.Cg == 128) && (k.W % THIN_TW) == 0 &&
            (long)k.N * ((k.H + WTH - 1) / WTH) * (k.W / THIN_TW) >= 64;
 }
 
@@ -680,7 +679,7 @@ int launch_wgrad_thin(Wg3K& k, hipStream_t st, int* nsplit, bool dry)
 // bf16, Cin == 8, Cg == 64, any window of at most 7 x 7 taps at stride 1 or 2 (not the 3x3 / stride-1 / same-size case of the kernel above)
 static bool wgrad_thin_taps_geom(const mg_wgrad_desc* d, WgT& k, long& ntiles, int& tiles_y, int& tiles_x, int& nblocks)
 {
-    if (g_mg_conv_thin < 2 || d->dtype != MG_BF16 || d->Cin != 8 || d->Cg != 64 || d->isy != d->isx || (d->isy != 1 && d->isy != 2)) return false;
+    if (mg_opt(MG_OPT_CONV_THIN) < 2 || d->dtype != MG_BF16 || d->Cin != 8 || d->Cg != 64 || d->isy != d->isx || (d->isy != 1 && d->isy != 2)) return false;
     if (d->ntaps > 52) return false;
     int dy0 = 127, dx0 = 127, dy1 = -128, dx1 = -128;
     for (int t = 0; t < d->ntaps; ++t) {

@@ -17,9 +17,9 @@
 // sample pivot makes the partial sums grow like n |k| instead of sqrt(n) sigma.  Per-thread fp64 accumulation (no pivot needed) was
 // measured too: same results, stats_stage1_vec 17.8 -> 21.7 us per launch (+0.24 ms per step), not kept.
 #include "mg_common.h"
+#include "mg_options.h"
 #include <type_traits>
 
-int g_mg_norm_bwd_vec = 1;        // mg_set_option(19, v): 0 = the norm backward reduction stays on the 8-byte quad kernel
 
 namespace {
 
@@ -679,7 +679,7 @@ int run_reduce(const void* x, const void* dh, const void* h, const void* g1, con
 {
     const StatGeom sg = stat_geom(G, P, C);
     dim3 grid(sg.nchunks, G);
-    if (g_mg_norm_bwd_vec && vec_geom_ok<T>(C) && act != MG_ACT_TANH) {
+    if (mg_opt(MG_OPT_NORM_BWD_VEC) && vec_geom_ok<T>(C) && act != MG_ACT_TANH) {
         // (d[gamma|beta] rows are 32-channel blocks; a thread's VEC channels start at a multiple of VEC and stay inside one block)
         const float neg = act == MG_ACT_NONE ? 1.f : (act == MG_ACT_RELU ? 0.f : slope);
         const bool hh = h != nullptr && act != MG_ACT_NONE;

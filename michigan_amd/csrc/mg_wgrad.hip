@@ -14,10 +14,9 @@
 // Partial sums are accumulated into the fp32 dW with hardware float atomics.
 #include "mg_common.h"
 #include "mg_wgrad_common.h"
+#include "mg_options.h"
 
-int g_mg_wgrad3x3 = 1;     // mg_set_option(3, v): 0 = always the generic tap-per-workgroup kernel
 
-int g_mg_wgrad_min_stages = 32;      // mg_set_option(18, v): stages (of 32 / 16 pixels) a split of the generic kernel keeps at least
 
 namespace {
 
@@ -324,7 +323,8 @@ int launch_wgrad(WgK& k, hipStream_t st, int* nsplit = nullptr, bool dry = false
         S = (int)((1536 + base - 1) / base);                 // ~6 workgroups per CU in flight
         // >= 32 stages per split: every split ends with a pass of atomics over its 128 x 128 tile; with the 8-stage floor the mid-size
         // stride-2 / 1x1 layers ran 1500 workgroups of 12 stages and took 0.10 ms where 32-stage splits take 0.065 (tools/variant_sweep.py)
-        int maxS = (k.K + KP * g_mg_wgrad_min_stages - 1) / (KP * g_mg_wgrad_min_stages);
+        const int min_stages = mg_opt(MG_OPT_WGRAD_MIN_STAGES);
+        int maxS = (k.K + KP * min_stages - 1) / (KP * min_stages);
         if (base * maxS < 256) {                               // ... unless that leaves CUs idle (tiny layers): down to 4 stages per split
             const int fill = (int)((256 + base - 1) / base), floor4 = (k.K + KP * 4 - 1) / (KP * 4);
             maxS = fill < floor4 ? fill : floor4;
@@ -380,7 +380,7 @@ int route_wgrad(const mg_wgrad_desc* d, hipStream_t st, float* dw, float* dbias,
         if (std3x3 && wgrad_thin_applies(k3)) return launch_wgrad_thin(k3, st, nsplit, dry);
     }
     if (wgrad_thin_taps_applies(d)) return launch_wgrad_thin_taps(d, st, dw, dbias, det_stride, nsplit, dry);
-    if (g_mg_wgrad3x3 && d->dtype == MG_BF16 && (d->flags & 1) && d->ntaps == 9 && d->isy == 1 && d->isx == 1 &&
+    if (mg_opt(MG_OPT_WGRAD3X3) && d->dtype == MG_BF16 && (d->flags & 1) && d->ntaps == 9 && d->isy == 1 && d->isx == 1 &&
         d->Hin == d->Hj && d->Win == d->Wj && (d->Win == 16 || d->Win % 32 == 0) && (d->Hin * d->Win) % 32 == 0 &&
         d->Cin >= 64 && d->Cg >= 64) {
         bool std3x3 = true;

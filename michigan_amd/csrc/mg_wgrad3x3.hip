@@ -16,8 +16,6 @@
 #include "mg_conv_common.h"
 #include "mg_wgrad_common.h"
 
-extern int g_mg_wgrad3x3_probe;    // mg_conv.hip, mg_set_option(12, v): 1 = launch the stamped build of wgrad3x3_kernel<2, 2>
-int g_mg_wgrad3x3_stripe = 64;     // mg_set_option(24, v): pixel width of the column stripes the stages walk (0 = plain raster order over whole image rows)
 
 namespace {
 
@@ -25,7 +23,7 @@ typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_p;
 
-// Measurement build (mg_set_option(12, 1) + the stamp buffer of mg_set_option(13 / 14)): s_memrealtime stamps around the vmcnt wait,
+// Measurement build (MG_OPT_PROBE_WGRAD3X3 + the stamp buffer of MG_OPT_PROBE_ADDR_LO / _HI): s_memrealtime stamps around the vmcnt wait,
 // the barrier, the DMA issue (address arithmetic included) and the MFMA block of every stage; tools/probe_wgrad3x3.py.
 __device__ unsigned long long* g_mg_wg3_probe_out = nullptr;
 __device__ __forceinline__ unsigned long long wg3_stamp()
@@ -331,7 +329,8 @@ int launch3(Wg3K& k, hipStream_t st, int* nsplit, bool dry)
     constexpr size_t LDS = 4 * (size_t)STAGE + 4096;
     k.tiles_m = (k.Cg + TM - 1) / TM;
     k.tiles_n = (k.Cin + TN - 1) / TN;
-    k.stripe_w = (!W16 && g_mg_wgrad3x3_stripe >= 32 && (g_mg_wgrad3x3_stripe % 32) == 0 && k.W > g_mg_wgrad3x3_stripe && (k.W % g_mg_wgrad3x3_stripe) == 0) ? g_mg_wgrad3x3_stripe : k.W;
+    const int stripe = mg_opt(MG_OPT_WGRAD3X3_STRIPE);
+    k.stripe_w = (!W16 && stripe >= 32 && (stripe % 32) == 0 && k.W > stripe && (k.W % stripe) == 0) ? stripe : k.W;
     const long base = 3L * k.tiles_m * k.tiles_n;
     // Split-K: every split adds one pass of fp32 atomics over the whole dW (~1.5 TB/s), while the main loop is
     // already near its rate with ~1.5 workgroups per CU (tools/wgrad_split_sweep.py): use ~384 workgroups, more
@@ -360,7 +359,7 @@ int launch3(Wg3K& k, hipStream_t st, int* nsplit, bool dry)
     mg_raise_lds_cap(reinterpret_cast<const void*>(kern), (int)LDS_HALF_CU);
 #if MG_PROBES
     if constexpr (MT == 2 && NT == 2 && !W16) {
-        if (g_mg_wgrad3x3_probe) {
+        if (mg_opt(MG_OPT_PROBE_WGRAD3X3)) {
             auto pk = wgrad3x3_kernel<MT, NT, W16, true>;
             mg_raise_lds_cap(reinterpret_cast<const void*>(pk), (int)LDS);
             hipLaunchKernelGGL(pk, dim3((unsigned)nblk), dim3(256), LDS, st, k);

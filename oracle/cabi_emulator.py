@@ -82,7 +82,8 @@ class EmulatorBackend:
 
     # -- bookkeeping ---------------------------------------------------------
     def mg_abi_version(self):
-        return 5
+        from michigan_amd import _cabi
+        return _cabi.MG_ABI_VERSION
 
     def mg_wgrad_det_workspace(self, d):
         return 16            # the emulator's weight gradient is a deterministic float64 sum: nothing to size
@@ -623,7 +624,12 @@ class EmulatorBackend:
         _view(out, (rows, cols), torch.float32)[:] = ((gv - sv * uv) / sg).float()
         return 0
 
-    def mg_set_option(self, key, value):
+    def mg_set_option(self, key, value):          # the switches select kernels: inert here, kept only so that they read back
+        vars(self).setdefault("_options", {})[key] = value
+        return 0
+
+    def mg_get_option(self, key, value):          # `value`: ctypes.byref(c_int32)
+        value._obj.value = vars(self).get("_options", {}).get(key, 0)
         return 0
 
     def mg_adam_step(self, param, grad, m, v, numel, lr, b1, b2, eps, step, gscale, stream=None):

@@ -39,7 +39,7 @@ D_BUFFERS = ("discriminator_0.model1.0.0.weight_u", "discriminator_1.model3.0.0.
 LOSS_KEYS = ("GAN", "GAN_Feat", "VGG", "ORIENT", "D_Fake", "D_real")
 # Tolerance for everything behind an optimiser step on the HIP fp32 kernels (Adam with beta1 = 0 is a sign function at the first step:
 # which near-zero gradients flip is rounding luck in ANY fp32 implementation, the reference's own CPU run included).
-# tools/noise_probe.py runs the protocol on MI355X with the two conv pipelines and reports the distance to the reference's CPU run:
+# A probe (retired with the register-staged conv pipeline it switched to) ran the protocol on MI355X with the two conv pipelines and reported the distance to the reference's CPU run:
 #   rounds 3 / 4 with ONE fp32 accumulation chain per output (profiles/r03_noise_probe.txt, r04_noise_probe_one_chain.txt): running
 #     statistics 2.6e-2 ... 3.0e-2, iteration-1 losses 1.2e-2 ... 1.5e-2, and the two pipelines 2.7e-2 ... 4.2e-2 apart from each other;
 #   round 4 with two-level fp32 sums (profiles/r04_noise_probe.txt; forward error below ATen's): fixture A running statistics 8.6e-3,

@@ -72,3 +72,99 @@ def test_kernels_are_gfx950_code_objects(lib_path):
     blob = open(lib_path, "rb").read()
     assert b"amdgcn-amd-amdhsa--gfx950" in blob
     assert b"gfx942" not in blob and b"sm_" not in blob[:0]
+
+
+def _header_options():
+    src = open(os.path.join(ROOT, "include", "michigan_hip.h")).read()
+    body = re.search(r"enum mg_option \{(.*?)\};", src, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    return {name: int(num) for name, num in re.findall(r"\b(MG_OPT_[A-Z0-9_]+)\s*=\s*(\d+)", body)}
+
+
+# defaults of the parent's definitions (the `int g_mg_* = N;` the table replaced), carried here as the pin
+OPTION_DEFAULTS = {1: 1, 2: 1, 3: 1, 4: 1, 5: 1, 7: 1, 19: 1, 22: 1, 6: 2, 8: 2, 18: 32, 24: 64}
+RETIRED_KEYS = (0, 9, 17)
+PROBE_KEYS = (10, 12, 13, 14, 15, 21, 23)
+
+
+def test_option_names_mirror_the_header():
+    from michigan_amd import _cabi
+    header = _header_options()
+    mirror = {"MG_" + k: v for k, v in vars(_cabi).items() if k.startswith("OPT_")}
+    assert len(header) >= len(OPTION_DEFAULTS) + len(PROBE_KEYS)
+    assert mirror == header
+    assert len(set(header.values())) == len(header), "two switches share a number"
+    assert set(OPTION_DEFAULTS) | set(PROBE_KEYS) == set(header.values())
+    probes = {v for k, v in header.items() if k.startswith("MG_OPT_PROBE_")}
+    assert probes == set(PROBE_KEYS)
+
+
+def test_options_defaults_ranges_and_gating(lib_path):
+    """mg_get_option on a freshly loaded library returns the defaults; set checks the range and reads back; the product
+    library refuses retired and MG_PROBES-only keys, by set and by get."""
+    from michigan_amd import _cabi
+    be = _cabi.HipBackend(lib_path)
+    for key, want in OPTION_DEFAULTS.items():
+        assert _cabi.get_option(key, be) == want, key
+
+    def accepts(key, v):
+        be.mg_set_option(key, v)
+        assert _cabi.get_option(key, be) == v, (key, v)
+
+    def refuses(key, v):
+        before = _cabi.get_option(key, be) if key in OPTION_DEFAULTS else None
+        with pytest.raises(RuntimeError, match=r"unknown key/value %d/%d" % (key, v)):
+            be.mg_set_option(key, v)
+        if before is not None:
+            assert _cabi.get_option(key, be) == before, "a refused value was stored"
+
+    try:
+        accepts(6, 0); accepts(6, 2); refuses(6, 3)
+        accepts(18, 1); accepts(18, 1024); refuses(18, 0); refuses(18, 1025)
+        accepts(24, 0); accepts(24, 4096); refuses(24, 48); refuses(24, 4128)
+        for key in (1, 2, 3, 4, 5, 7, 19, 22):
+            refuses(key, -1); refuses(key, 2)
+            accepts(key, 0); accepts(key, 1)
+        for key in RETIRED_KEYS + PROBE_KEYS + (11, 16, 20, 25, -1, 1 << 20):
+            for v in (0, 1):
+                refuses(key, v)
+            with pytest.raises(RuntimeError, match="mg_get_option"):
+                _cabi.get_option(key, be)
+        with pytest.raises(RuntimeError, match="mg_get_option"):
+            be.mg_get_option(1, None)
+    finally:
+        for key, v in OPTION_DEFAULTS.items():
+            be.mg_set_option(key, v)
+
+
+def test_options_scope_restores_what_it_read(lib_path):
+    from michigan_amd import _cabi
+    be = _cabi.HipBackend(lib_path)
+    thin, stripe = _cabi.OPT_CONV_THIN, _cabi.OPT_WGRAD3X3_STRIPE
+    be.mg_set_option(thin, 1)                       # not the default: the scope must put back THIS, not a remembered 2
+    try:
+        with pytest.raises(ZeroDivisionError):
+            with _cabi.options({thin: 0, stripe: 128}, be):
+                assert (_cabi.get_option(thin, be), _cabi.get_option(stripe, be)) == (0, 128)
+                1 / 0
+        assert (_cabi.get_option(thin, be), _cabi.get_option(stripe, be)) == (1, 64)
+        with _cabi.options({thin: 2}, be):
+            assert _cabi.get_option(thin, be) == 2
+        assert _cabi.get_option(thin, be) == 1
+        with pytest.raises(RuntimeError, match="unknown key/value"):      # a refused value inside the set: what was set before it is undone
+            with _cabi.options({stripe: 32, thin: 7}, be):
+                pass
+        assert (_cabi.get_option(thin, be), _cabi.get_option(stripe, be)) == (1, 64)
+    finally:
+        be.mg_set_option(thin, OPTION_DEFAULTS[thin])
+
+
+def test_emulator_options_read_back():
+    from michigan_amd import _cabi
+    from oracle.cabi_emulator import EmulatorBackend
+    em = EmulatorBackend()
+    assert em.mg_abi_version() == _cabi.MG_ABI_VERSION
+    assert _cabi.get_option(_cabi.OPT_CONV_THIN, em) == 0           # never set: 0, the emulator keeps no list of defaults
+    with _cabi.options({_cabi.OPT_CONV_THIN: 1}, em):
+        assert _cabi.get_option(_cabi.OPT_CONV_THIN, em) == 1
+    assert _cabi.get_option(_cabi.OPT_CONV_THIN, em) == 0

@@ -219,11 +219,8 @@ def test_wgrad3x3_kernel_row_tiles(N, H, W, cin, cg, want_bias):
         _close(f"wgrad3x3 {(N, H, W, cin, cg)} {name}", a, r, 2e-3)
     if not os.environ.get("MG_TEST_DRYRUN"):
         from michigan_amd import _cabi
-        _cabi.backend().mg_set_option(3, 0)                       # same problem on the generic kernel
-        try:
+        with _cabi.options({_cabi.OPT_WGRAD3X3: 0}):               # same problem on the generic kernel
             gen = fn(x.cuda(), dy.cuda())
-        finally:
-            _cabi.backend().mg_set_option(3, 1)
         _close(f"wgrad3x3 vs generic {(N, H, W, cin, cg)}", hip[0], gen[0].cpu(), 2e-3)
 
 
@@ -383,7 +380,8 @@ def test_conv_matches_miopen_large_bf16():
     _close("linearity", y2, 2 * y, 2.0 ** -7)
 
 
-@pytest.mark.parametrize("variant,opts", [("halo16", {2: 1, 4: 1}), ("halo8", {2: 1, 4: 0}), ("generic", {2: 0, 4: 0})])
+@pytest.mark.parametrize("variant,opts", [("halo16", {"OPT_CONV_HALO": 1, "OPT_CONV_HALO_BIG": 1}), ("halo8", {"OPT_CONV_HALO": 1, "OPT_CONV_HALO_BIG": 0}),
+                                          ("generic", {"OPT_CONV_HALO": 0, "OPT_CONV_HALO_BIG": 0})])
 @pytest.mark.parametrize("with_bias", [False, True], ids=["nobias", "bias"])
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 def test_conv_race_screen(variant, opts, with_bias, dt):
@@ -399,17 +397,11 @@ def test_conv_race_screen(variant, opts, with_bias, dt):
     wr = w if dt == "f32" else w.bfloat16().float()
     ref = torch.nn.functional.conv2d(x.float().permute(0, 3, 1, 2), wr, b, padding=1).permute(0, 2, 3, 1)
     thr = 2e-3 if dt == "f32" else 0.06
-    be = _cabi.backend()
-    try:
-        for k, v in opts.items():
-            be.mg_set_option(k, v)
+    with _cabi.options({getattr(_cabi, k): v for k, v in opts.items()}):
         bad = 0
         for _ in range(40):
             y = ops.conv2d(x, w, b, padding=1).float()
             bad += int(((y - ref).abs() > thr).sum() > 0)
-    finally:
-        be.mg_set_option(2, 1)
-        be.mg_set_option(4, 1)
     assert bad == 0, f"{variant}: {bad} of 40 runs had wrong tiles"
 
 
@@ -471,13 +463,9 @@ def test_halo_conv_ragged_geometry(cin, cout, H, W, big, dt):
     w = (torch.randn(cout, cin, 3, 3, generator=g) / (3 * cin ** 0.5)).cuda()
     b = torch.randn(cout, generator=g).cuda()
     gy = torch.randn(4, H, W, cout, generator=g).to(DT[dt]).cuda()
-    be = _cabi.backend()
-    be.mg_set_option(4, big)
-    try:
+    with _cabi.options({_cabi.OPT_CONV_HALO_BIG: big}):
         y = ops.conv2d(x, w, b, padding=1, act=ops.ACT_LRELU)
         (dx,) = torch.autograd.grad(y, x, gy)
-    finally:
-        be.mg_set_option(4, 1)
     xr = x.detach().float().permute(0, 3, 1, 2).contiguous()
     wr = w if dt == "f32" else w.bfloat16().float()
     yr = torch.nn.functional.leaky_relu(torch.nn.functional.conv2d(xr, wr, b, padding=1), 0.2)
@@ -497,20 +485,16 @@ def test_halo_conv_ragged_geometry(cin, cout, H, W, big, dt):
 def test_thin_conv_8_channel_input(cout, H, W, act, with_bias):
     """The register-weight kernel for 3x3 convs over an 8-channel bf16 map (SPADE's mlp_shared): heights that are not
     multiples of its 8-row tile, 64 / 96 / 128 output channels, every fused activation, against torch's fp32 convolution
-    and against the tap-list kernel it replaces (mg_set_option(6, 0))."""
+    and against the tap-list kernel it replaces (OPT_CONV_THIN = 0)."""
     from michigan_amd import ops, _cabi
     g = torch.Generator().manual_seed(cout + H)
     x = torch.randn(4, H, W, 8, generator=g).bfloat16().cuda()
     w = (torch.randn(cout, 8, 3, 3, generator=g) / 8).cuda()
     b = torch.randn(cout, generator=g).cuda() if with_bias else None
     code = {"relu": ops.ACT_RELU, "lrelu": ops.ACT_LRELU, "none": ops.ACT_NONE}[act]
-    be = _cabi.backend()
     y = ops.conv2d(x, w, b, padding=1, act=code)
-    be.mg_set_option(6, 0)
-    try:
+    with _cabi.options({_cabi.OPT_CONV_THIN: 0}):
         y_taps = ops.conv2d(x, w, b, padding=1, act=code)
-    finally:
-        be.mg_set_option(6, 2)
     yr = torch.nn.functional.conv2d(x.float().permute(0, 3, 1, 2), w.bfloat16().float(), b, padding=1)
     yr = {"relu": torch.relu, "lrelu": lambda t: torch.nn.functional.leaky_relu(t, 0.2), "none": lambda t: t}[act](yr)
     _close("thin conv vs torch", y, yr.permute(0, 2, 3, 1), TOL["bf16"])
@@ -520,18 +504,14 @@ def test_thin_conv_8_channel_input(cout, H, W, act, with_bias):
 @pytest.mark.parametrize("cg,H,W,want_bias", [(128, 72, 64, True), (64, 45, 96, True), (128, 61, 128, False), (64, 128, 32, True)], ids=str)
 def test_thin_wgrad_8_channel_input(cg, H, W, want_bias):
     """Weight (and bias) gradient of the same layers: register-accumulator kernel vs torch's fp32 autograd on the same
-    bf16 operands and vs the generic kernel (mg_set_option(6, 0)); heights that are not multiples of its 4-row tile."""
+    bf16 operands and vs the generic kernel (OPT_CONV_THIN = 0); heights that are not multiples of its 4-row tile."""
     from michigan_amd import ops, _cabi
     g = torch.Generator().manual_seed(cg + H)
     x = torch.randn(4, H, W, 8, generator=g).bfloat16().cuda()
     dy = torch.randn(4, H, W, cg, generator=g).bfloat16().cuda()
-    be = _cabi.backend()
     res = ops.conv_wgrad(x, dy, 3, 3, 1, 1, want_bias=want_bias)
-    be.mg_set_option(6, 0)
-    try:
+    with _cabi.options({_cabi.OPT_CONV_THIN: 0}):
         res_taps = ops.conv_wgrad(x, dy, 3, 3, 1, 1, want_bias=want_bias)
-    finally:
-        be.mg_set_option(6, 2)
     w = torch.zeros(cg, 8, 3, 3, device="cuda", requires_grad=True)
     b = torch.zeros(cg, device="cuda", requires_grad=True)
     torch.nn.functional.conv2d(x.float().permute(0, 3, 1, 2), w, b, padding=1).backward(dy.float().permute(0, 3, 1, 2))
@@ -558,7 +538,7 @@ THIN_TAPS_CASES = [  # N, H, W, cout, k, stride, pad, act, bias   (8-channel bf1
 def test_thin_taps_conv_and_wgrad_any_window(case):
     """The LDS-weight kernels for ANY <= 7x7 window over an 8-channel bf16 map (7x7 first conv, 4x4 / stride-2 discriminator input
     conv, 3x3 / stride-2 encoder input conv): forward against torch's fp32 convolution and against the tap-list kernel
-    (mg_set_option(6, 1)); weight / bias gradients (64-channel dY) against torch's fp32 autograd and the generic kernel."""
+    (OPT_CONV_THIN = 1); weight / bias gradients (64-channel dY) against torch's fp32 autograd and the generic kernel."""
     from michigan_amd import ops, _cabi
     N, H, W, cout, k, stride, pad, act, with_bias = case
     g = torch.Generator().manual_seed(H * 7 + W + cout)
@@ -566,13 +546,9 @@ def test_thin_taps_conv_and_wgrad_any_window(case):
     w = (torch.randn(cout, 8, k, k, generator=g) / (2.0 * k)).cuda()
     b = torch.randn(cout, generator=g).cuda() if with_bias else None
     code = {"relu": ops.ACT_RELU, "lrelu": ops.ACT_LRELU, "none": ops.ACT_NONE}[act]
-    be = _cabi.backend()
     y = ops.conv2d(x, w, b, stride=stride, padding=pad, act=code)
-    be.mg_set_option(6, 1)
-    try:
+    with _cabi.options({_cabi.OPT_CONV_THIN: 1}):
         y_taps = ops.conv2d(x, w, b, stride=stride, padding=pad, act=code)
-    finally:
-        be.mg_set_option(6, 2)
     yr = torch.nn.functional.conv2d(x.float().permute(0, 3, 1, 2), w.bfloat16().float(), b, stride=stride, padding=pad)
     yr = {"relu": torch.relu, "lrelu": lambda t: torch.nn.functional.leaky_relu(t, 0.2), "none": lambda t: t}[act](yr)
     assert tuple(y.shape) == tuple(yr.permute(0, 2, 3, 1).shape)
@@ -583,11 +559,8 @@ def test_thin_taps_conv_and_wgrad_any_window(case):
     dy = torch.randn(N, yr.shape[2], yr.shape[3], 64, generator=g).bfloat16().cuda()
     res = ops.conv_wgrad(x, dy, k, k, stride, pad, want_bias=with_bias)
     res2 = ops.conv_wgrad(x, dy, k, k, stride, pad, want_bias=with_bias)
-    be.mg_set_option(6, 1)
-    try:
+    with _cabi.options({_cabi.OPT_CONV_THIN: 1}):
         res_taps = ops.conv_wgrad(x, dy, k, k, stride, pad, want_bias=with_bias)
-    finally:
-        be.mg_set_option(6, 2)
     wz = torch.zeros(64, 8, k, k, device="cuda", requires_grad=True)
     bz = torch.zeros(64, device="cuda", requires_grad=True)
     torch.nn.functional.conv2d(x.float().permute(0, 3, 1, 2), wz, bz, stride=stride, padding=pad).backward(dy.float().permute(0, 3, 1, 2))
@@ -613,21 +586,17 @@ def test_thin_taps_conv_and_wgrad_any_window(case):
 def test_few_output_channel_convs_over_64_channels(case):
     """The 16-row MFMA kernel for <= 16 GEMM rows over a 64-channel bf16 input (mg_conv_dot.hip): conv_img (64 -> 3, tanh) forward and
     the data gradients that end in an 8-channel network input (stride 1, and the four parity classes of a stride-2 conv with strided
-    stores), ragged tiles, against torch fp32 and against the tap-list kernel (mg_set_option(8, 1))."""
+    stores), ragged tiles, against torch fp32 and against the tap-list kernel (OPT_CONV_DOT = 1)."""
     from michigan_amd import ops, _cabi
     name, cnarrow, k, stride, pad = case
     g = torch.Generator().manual_seed(len(name) + k)
-    be = _cabi.backend()
     if name == "img":
         x = torch.randn(3, 72, 100, 64, generator=g).bfloat16().cuda()
         w = (torch.randn(3, 64, 3, 3, generator=g) / 24).cuda()
         b = torch.randn(3, generator=g).cuda()
         y = ops.conv2d(x, w, b, padding=1, act=ops.ACT_TANH)
-        be.mg_set_option(8, 1)
-        try:
+        with _cabi.options({_cabi.OPT_CONV_DOT: 1}):
             y_taps = ops.conv2d(x, w, b, padding=1, act=ops.ACT_TANH)
-        finally:
-            be.mg_set_option(8, 2)
         yr = torch.tanh(torch.nn.functional.conv2d(x.float().permute(0, 3, 1, 2), w.bfloat16().float(), b, padding=1)).permute(0, 2, 3, 1)
         _close("few-output conv vs torch", y[..., :3], yr, TOL["bf16"])
         _close("few-output conv vs tap-list kernel", y, y_taps, TOL["bf16"])
@@ -638,12 +607,9 @@ def test_few_output_channel_convs_over_64_channels(case):
     y = ops.conv2d(x, w, None, stride=stride, padding=pad)
     gy = torch.randn(y.shape, generator=g).bfloat16().cuda()
     (dx,) = torch.autograd.grad(y, x, gy)
-    be.mg_set_option(8, 1)
-    try:
+    with _cabi.options({_cabi.OPT_CONV_DOT: 1}):
         y2 = ops.conv2d(x, w, None, stride=stride, padding=pad)
         (dx_taps,) = torch.autograd.grad(y2, x, gy)
-    finally:
-        be.mg_set_option(8, 2)
     xr = x.detach().float().permute(0, 3, 1, 2).requires_grad_(True)
     yr = torch.nn.functional.conv2d(xr, w.bfloat16().float(), None, stride=stride, padding=pad)
     (dxr,) = torch.autograd.grad(yr, xr, gy.float().permute(0, 3, 1, 2))
@@ -761,15 +727,13 @@ def test_gabor_argmax_and_orientation_loss(dt):
 
 @pytest.mark.parametrize("epi", ["plain", "plain+resid", "spade"])
 def test_wide_epilogue_stores_are_bit_identical_to_quad_stores(epi):
-    """mg_set_option(7, v): the half-wave quad exchange (v_permlane32_swap) + 16-byte stores against the 8-byte-per-quad
+    """OPT_CONV_WIDE: the half-wave quad exchange (v_permlane32_swap) + 16-byte stores against the 8-byte-per-quad
     stores it replaces, bf16, on a halo-kernel shape and a generic-kernel shape -- same bits (only the store width changes)."""
     from michigan_amd import _cabi, ops
-    be = _cabi.backend()
     g = torch.Generator().manual_seed(31)
     outs = []
     for v in (1, 0):
-        be.mg_set_option(7, v)
-        try:
+        with _cabi.options({_cabi.OPT_CONV_WIDE: v}):
             res = []
             for (n, h, w, cin, cout, k, s, p) in [(2, 48, 64, 64, 128, 3, 1, 1), (2, 33, 29, 64, 72, 4, 2, 1)]:
                 gg = torch.Generator().manual_seed(n * h + cout)
@@ -792,8 +756,6 @@ def test_wide_epilogue_stores_are_bit_identical_to_quad_stores(epi):
                 res.append(y.detach().clone())
             torch.cuda.synchronize()
             outs.append(res)
-        finally:
-            be.mg_set_option(7, 1)
     for a, b_ in zip(*outs):
         assert torch.equal(a.view(torch.int16), b_.view(torch.int16))
 
@@ -1315,23 +1277,20 @@ def test_self_attention_matches_contract(hip_backend, dt):
 
 def test_halo64_matches_the_shipped_halo_kernel_bitwise(hip_backend):
     """csrc/mg_conv_halo64.hip (3x3 convolutions over exactly 64 input channels: weights in registers, strips of 16x16 tiles per workgroup)
-    against the kernel it replaces (mg_set_option(22, 0): conv3x3_halo_kernel<bf16, PLAIN, 1, 2> / <2, 2>): same K order, so BITWISE equal --
+    against the kernel it replaces (OPT_CONV_HALO64 = 0: conv3x3_halo_kernel<bf16, PLAIN, 1, 2> / <2, 2>): same K order, so BITWISE equal --
     every epilogue case it takes ({no aux} x {none, relu, lrelu}, residual, ReLU mask and LeakyReLU mask of a data gradient), 64 -> 64 and
     64 -> 128, several strip splits (batch 1: eight segments per row band; batch 3: an odd number of workgroups, no XCD remap), non-square
     images, image borders on all four sides; and against the float64 contract for one case.  Shapes that the new kernel does not take
     (ragged tiles, too few tiles) must still run (on the shipped kernel)."""
-    from michigan_amd import ops
+    from michigan_amd import _cabi, ops
     be = hip_backend
     g = torch.Generator().manual_seed(11)
 
     def both(fn):
         outs = []
         for on in (1, 0):
-            be.mg_set_option(22, on)
-            try:
+            with _cabi.options({_cabi.OPT_CONV_HALO64: on}, be):
                 outs.append(fn().clone())
-            finally:
-                be.mg_set_option(22, 1)
         torch.cuda.synchronize()
         return outs
 
@@ -1364,21 +1323,19 @@ def test_halo64_matches_the_shipped_halo_kernel_bitwise(hip_backend):
     times = []
     with torch.no_grad():
         for on in (1, 0):
-            be.mg_set_option(22, on)
-            for _ in range(3):
-                ops.conv2d_infer(x, wt, b, padding=1, act=ops.ACT_RELU)
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(10):
-                ops.conv2d_infer(x, wt, b, padding=1, act=ops.ACT_RELU)
-            e.record(); torch.cuda.synchronize()
-            times.append(s.elapsed_time(e) / 10 * 1e3)
-        be.mg_set_option(22, 1)
+            with _cabi.options({_cabi.OPT_CONV_HALO64: on}, be):
+                for _ in range(3):
+                    ops.conv2d_infer(x, wt, b, padding=1, act=ops.ACT_RELU)
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                for _ in range(10):
+                    ops.conv2d_infer(x, wt, b, padding=1, act=ops.ACT_RELU)
+                e.record(); torch.cuda.synchronize()
+                times.append(s.elapsed_time(e) / 10 * 1e3)
     print("64 -> 64 @ 8x512^2 (bias + ReLU): halo64 %.1f us, shipped halo kernel %.1f us; %.2f TB/s of algorithmic traffic" % (times[0], times[1], 2 * x.numel() * 2 / times[0] / 1e6))
     assert times[0] < times[1]
     # contract check of one case against the float64 emulator
     from oracle.cabi_emulator import EmulatorBackend
-    from michigan_amd import _cabi
     xs = torch.randn(2, 512, 512, 64, generator=g).to(torch.bfloat16)
     ws = (torch.randn(64, 64, 3, 3, generator=g) * 0.05)
     bs = torch.randn(64, generator=g)

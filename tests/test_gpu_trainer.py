@@ -139,6 +139,6 @@ def test_deterministic_mode_makes_a_training_step_bit_reproducible(hip_backend, 
     # generator's sign-like Adam update: last-bit differences of the generator gradients flip single weights, compared loosely.)
     gs = c[0].abs().max().item()
     assert (a[0] - c[0]).abs().max().item() <= (2e-5 if dtype == "fp32" else 2e-3) * gs
-    # (tools/noise_probe.py: two correct runs of this step differ by 4e-2 in the D losses; single gradient entries by more)
+    # (profiles/r04_noise_probe.txt: two correct runs of this step differ by 4e-2 in the D losses; single gradient entries by more)
     assert (a[1] - c[1]).abs().max().item() <= 0.2 * c[1].abs().max().item()
     assert torch.nn.functional.cosine_similarity(a[1], c[1], dim=0).item() > 0.99

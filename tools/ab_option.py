@@ -1,4 +1,4 @@
-"""A/B a kernel option on the full training step inside one process: tools/ab_option.py <key> [value_a value_b] (GPU box)."""
+"""A/B a kernel option (its number in enum mg_option) on the full training step inside one process: tools/ab_option.py <key> [value_a value_b] (GPU box)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import michigan_amd  # noqa: F401
@@ -16,8 +16,8 @@ def step():
 for _ in range(3): step()
 for rep in range(3):
     for v in vals:
-        _cabi.backend().mg_set_option(key, v)
-        step(); torch.cuda.synchronize(); t0 = time.perf_counter()
-        for _ in range(6): step()
-        torch.cuda.synchronize()
+        with _cabi.options({key: v}):
+            step(); torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(6): step()
+            torch.cuda.synchronize()
         print(f"option {key} = {v}: {(time.perf_counter() - t0) / 6 * 1e3:.2f} ms/step", flush=True)

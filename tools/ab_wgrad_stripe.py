@@ -1,4 +1,4 @@
-"""wgrad3x3's stage order (mg_set_option(24, w): column stripes of w pixels; 0 = whole image rows): time, agreement, and -- under rocprofv3 --pmc -- L2 hit rate /
+"""wgrad3x3's stage order (OPT_WGRAD3X3_STRIPE = w: column stripes of w pixels; 0 = whole image rows): time, agreement, and -- under rocprofv3 --pmc -- L2 hit rate /
 fetched bytes per launch.   python tools/ab_wgrad_stripe.py            (timing + agreement)
                             rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace ... -- python tools/ab_wgrad_stripe.py pmc <w>   (one setting, 3 launches per shape)"""
 import os, sys
@@ -20,8 +20,9 @@ for name, cin, cout, hw in SHAPES:
     fn = lambda: ops.conv_wgrad(x, dy, 3, 3, 1, 1, want_bias=True)
     flops = 2.0 * n * hw * hw * cin * cout * 9
     row, ref = [], None
+    stripe0 = _cabi.get_option(_cabi.OPT_WGRAD3X3_STRIPE)
     for w in widths:
-        be.mg_set_option(24, w)
+        be.mg_set_option(_cabi.OPT_WGRAD3X3_STRIPE, w)
         for _ in range(1 if pmc else 3):
             out = fn()
         torch.cuda.synchronize()
@@ -39,6 +40,6 @@ for name, cin, cout, hw in SHAPES:
             ref = dw
         err = ((dw - ref).abs().max() / ref.abs().max()).item()
         row.append("w=%-3d %7.1f us %6.0f TF/s (max rel diff to w=0 %.1e)" % (w, us, flops / us / 1e6, err))
-    be.mg_set_option(24, 64)
+    be.mg_set_option(_cabi.OPT_WGRAD3X3_STRIPE, stripe0)
     if not pmc:
         print("%-24s %s" % (name, " | ".join(row)))

@@ -1,4 +1,4 @@
-"""Launch time of the 64-input-channel 3x3 convolutions (csrc/mg_conv_halo64.hip, mg_set_option(22, 1)) against the shipped halo kernel (22, 0):
+"""Launch time of the 64-input-channel 3x3 convolutions (csrc/mg_conv_halo64.hip, OPT_CONV_HALO64 = 1) against the shipped halo kernel (= 0):
 the launches of the step that take it -- 64 -> 64 (VGG conv1_2: bias + ReLU; up_3.conv_1: residual; their data gradients: ReLU / LeakyReLU mask) and
 64 -> 128 (data gradient of up_3.conv_0) -- at the batch sizes 8 / 4 / 1, kernel only (pre-packed weights, ops._launch_conv), HIP events over 20 launches.
 Prints us, TFLOP/s and TB/s of algorithmic traffic (input + output (+ auxiliary) tensors once).      python tools/bench_halo64.py"""
@@ -8,7 +8,6 @@ import michigan_amd  # noqa: F401
 import torch
 from michigan_amd import _cabi, ops
 
-be = _cabi.backend()
 g = torch.Generator().manual_seed(3)
 
 
@@ -46,8 +45,7 @@ for n in (8, 4, 1):
         nbytes = (x.numel() + out.numel() + (aux.numel() if kind in ("residual", "mask") else 0)) * 2
         row = []
         for on in (1, 0):
-            be.mg_set_option(22, on)
-            us = timed(fn)
+            with _cabi.options({_cabi.OPT_CONV_HALO64: on}):
+                us = timed(fn)
             row.append("%7.1f us (%6.1f TF/s, %.2f TB/s)" % (us, flops / us / 1e6, nbytes / us / 1e6))
-        be.mg_set_option(22, 1)
         print("N %d  64 -> %-3d %-10s %s | %s" % (n, cout, kind, row[0], row[1]))

@@ -46,7 +46,6 @@ def main():
     ap.add_argument("--n", type=int, default=4)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--only", default="")
-    ap.add_argument("--pipeline", type=int, default=1, help="0 register-staged, 1 LDS-DMA ring")
     ap.add_argument("--bigtiles", type=int, default=1)
     ap.add_argument("--halo", type=int, default=1)
     ap.add_argument("--data", default="randn", choices=["randn", "zeros", "relu"],
@@ -55,9 +54,8 @@ def main():
     a = ap.parse_args()
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     from michigan_amd import _cabi
-    _cabi.backend().mg_set_option(0, a.pipeline)
-    _cabi.backend().mg_set_option(1, a.bigtiles)
-    _cabi.backend().mg_set_option(2, a.halo)
+    _cabi.backend().mg_set_option(_cabi.OPT_CONV_BIGTILES, a.bigtiles)
+    _cabi.backend().mg_set_option(_cabi.OPT_CONV_HALO, a.halo)
     print(f"{'shape':28s} {'GF':>8s} | {'fwd ms':>8s} {'TF/s':>7s} | {'dgrad ms':>8s} {'TF/s':>7s} | {'wgrad ms':>8s} {'TF/s':>7s}")
     for name, cin, cout, k, s, p, H in SHAPES:
         if a.only and a.only not in name:

@@ -1,4 +1,4 @@
-"""A/B of the 8-channel-input 3x3 kernels (mg_set_option(6, v)) on the shapes the training step runs:
+"""A/B of the 8-channel-input 3x3 kernels (OPT_CONV_THIN) on the shapes the training step runs:
 forward (mlp_shared: 8 -> 128 + ReLU; encoder stems 8 -> 64) and weight gradient."""
 import sys
 import torch
@@ -20,7 +20,6 @@ def timeit(fn, reps=20):
 
 
 def main():
-    be = _cabi.backend()
     g = torch.Generator().manual_seed(0)
     for (n, hw, cout) in [(8, 512, 128), (8, 256, 128), (8, 128, 128), (8, 64, 128), (8, 32, 128), (8, 512, 64)]:
         x = torch.randn(n, hw, hw, 8, generator=g).bfloat16().cuda()
@@ -29,12 +28,11 @@ def main():
         gy = torch.randn(n, hw, hw, cout, generator=g).bfloat16().cuda()
         row = []
         for opt in (0, 1):
-            be.mg_set_option(6, opt)
-            with torch.no_grad():
-                tf = timeit(lambda: ops.conv2d(x, w, b, padding=1, act=ops.ACT_RELU))
-            tw = timeit(lambda: ops.conv_wgrad(x, gy, 3, 3, 1, 1, want_bias=True))
+            with _cabi.options({_cabi.OPT_CONV_THIN: opt}):
+                with torch.no_grad():
+                    tf = timeit(lambda: ops.conv2d(x, w, b, padding=1, act=ops.ACT_RELU))
+                tw = timeit(lambda: ops.conv_wgrad(x, gy, 3, 3, 1, 1, want_bias=True))
             row.append((tf, tw))
-        be.mg_set_option(6, 2)
         out_gb = n * hw * hw * cout * 2 / 1e9
         print(f"N{n} {hw}x{hw}x8 -> {cout}: fwd {row[0][0]*1e3:7.1f} -> {row[1][0]*1e3:7.1f} us ({out_gb / row[1][0] * 1e3:.2f} TB/s out)"
               f"   wgrad {row[0][1]*1e3:7.1f} -> {row[1][1]*1e3:7.1f} us ({out_gb / row[1][1] * 1e3:.2f} TB/s dy)")

@@ -2,7 +2,7 @@
 with the other (up-to-date) objects into michigan_amd/lib/variants/lib_<name>.so.  The GPU-side scripts swap it in, or a measurement tool
 loads it with MG_LIB=<path> (michigan_amd/_cabi.py).
     python tools/build_variant.py epi_scalar mg_conv_halo.hip -DMG_EPI_SCALAR=1
-    python tools/build_variant.py probes mg_conv.hip mg_conv_halo.hip mg_wgrad3x3.hip -DMG_PROBES=1      # tools/probe_halo.py, tools/probe_wgrad3x3.py"""
+    python tools/build_variant.py probes mg_api.hip mg_conv_halo.hip mg_wgrad3x3.hip -DMG_PROBES=1      # tools/probe_halo.py, tools/probe_wgrad3x3.py, tools/gate1_lone_wave.py, tools/dbg_halo64.py"""
 import os
 import subprocess
 import sys

@@ -16,7 +16,6 @@ from michigan_amd.model import Pix2PixTrainer
 FIX = sys.argv[1] if len(sys.argv) > 1 else "B"
 gold = np.load(os.path.join(ROOT, "tests", "golden", "trainer_%s.npz" % FIX))
 cfg = TP.CFGS[FIX]
-be = _cabi.backend()
 
 
 def run():
@@ -38,9 +37,8 @@ show("default", r0)
 if os.environ.get("DFAKE_SAVE"):
     np.savez(os.environ["DFAKE_SAVE"], **{k: np.asarray(v) for k, v in r0.items()})
 show("default, repeated (atomics' order only)", run())
-be.mg_set_option(0, 0); show("register-staged conv pipeline (option 0 = 0)", run()); be.mg_set_option(0, 1)
 ops.set_deterministic(True); show("MG_DETERMINISTIC: ordered split-K sums", run()); ops.set_deterministic(False)
 ops.FUSED_STATS_FINALIZE = False; show("statistics + finalize as three launches", run()); ops.FUSED_STATS_FINALIZE = True
-be.mg_set_option(3, 0); show("generic weight-gradient kernel (option 3 = 0)", run()); be.mg_set_option(3, 1)
-be.mg_set_option(2, 0); show("tap-list conv instead of the halo kernel (option 2 = 0)", run()); be.mg_set_option(2, 1)
+with _cabi.options({_cabi.OPT_WGRAD3X3: 0}): show("generic weight-gradient kernel (OPT_WGRAD3X3 = 0)", run())
+with _cabi.options({_cabi.OPT_CONV_HALO: 0}): show("tap-list conv instead of the halo kernels (OPT_CONV_HALO = 0)", run())
 ops.FUSE_LRELU_MASK = False; show("LeakyReLU mask not folded", run()); ops.FUSE_LRELU_MASK = True

@@ -1,6 +1,6 @@
 """VERDICT r5 "next" 2, gate 1: what does ONE wave per SIMD sustain in the halo conv's REAL K loop -- LDS-DMA weight ring live, per-tap vmcnt wait and
-s_barrier live, patch double buffer live, no epilogue (mg_set_option(10, 1): the kernel returns behind its K loop) -- against the shipped
-two residents per CU?  One resident per CU is forced by padding the launch's dynamic LDS request (mg_set_option(21, 81920)); the grid is the
+s_barrier live, patch double buffer live, no epilogue (OPT_PROBE_HALO_VARIANT = 1: the kernel returns behind its K loop) -- against the shipped
+two residents per CU?  One resident per CU is forced by padding the launch's dynamic LDS request (OPT_PROBE_HALO_LDSPAD = 81920); the grid is the
 product grid either way (tiles queue behind each other on a CU), so prologue and dispatch are in both numbers and only the epilogue is not.
 A persistent one-wave-per-SIMD kernel with a second accumulator set can hide the EPILOGUE behind the next tile's K loop; it cannot run the K loop
 itself faster than a lone wave runs it.  Gate: >= 1.38 PFLOP/s.     python tools/build_variant.py probes mg_conv.hip mg_conv_halo.hip mg_wgrad3x3.hip -DMG_PROBES=1
@@ -49,8 +49,7 @@ for name, cin, cout, hw, spade in SHAPES:
     with torch.no_grad():
         for pad, label in ((0, "2 residents"), (81920, "1 resident ")):
             for noepi in (0, 1):
-                be.mg_set_option(21, pad); be.mg_set_option(10, noepi)
-                us = timed(fn)
+                with _cabi.options({_cabi.OPT_PROBE_HALO_LDSPAD: pad, _cabi.OPT_PROBE_HALO_VARIANT: noepi}):
+                    us = timed(fn)
                 row.append("%s %s %7.1f (%7.1f us)" % (label, "K loop only" if noepi else "full       ", flops / us / 1e6, us))
-        be.mg_set_option(21, 0); be.mg_set_option(10, 0)
     print("%-24s %s" % (name, " | ".join(row)))

@@ -137,15 +137,12 @@ def report(tag, full=True):
 
 report("default")
 if args.variants:
-    be = _cabi.backend()
     for name, setter, restore in (
         ("FUSE_LRELU_MASK off", lambda: setattr(ops, "FUSE_LRELU_MASK", False), lambda: setattr(ops, "FUSE_LRELU_MASK", True)),
         ("FUSE_RELU_MASK off", lambda: setattr(ops, "FUSE_RELU_MASK", False), lambda: setattr(ops, "FUSE_RELU_MASK", True)),
         ("STATS_FROM_UPSAMPLE_SOURCE off", lambda: setattr(ops, "STATS_FROM_UPSAMPLE_SOURCE", False), lambda: setattr(ops, "STATS_FROM_UPSAMPLE_SOURCE", True)),
         ("FUSED_STATS_FINALIZE off", lambda: setattr(ops, "FUSED_STATS_FINALIZE", False), lambda: setattr(ops, "FUSED_STATS_FINALIZE", True)),
         ("SPADE pair node off", lambda: setattr(architecture, "PAIR_FUSED", False), lambda: setattr(architecture, "PAIR_FUSED", True)),
-        ("register-staged conv pipeline (option 0 = 0)", lambda: be.mg_set_option(0, 0), lambda: be.mg_set_option(0, 1)),
-        ("norm backward on the quad kernel (option 19 = 0)", lambda: be.mg_set_option(19, 0), lambda: be.mg_set_option(19, 1)),
         ("deterministic wgrad", lambda: ops.set_deterministic(True), lambda: ops.set_deterministic(False)),
     ):
         setter()
@@ -153,3 +150,5 @@ if args.variants:
             report(name, full=False)
         finally:
             restore()
+    with _cabi.options({_cabi.OPT_NORM_BWD_VEC: 0}):
+        report("norm backward on the quad kernel (OPT_NORM_BWD_VEC = 0)", full=False)

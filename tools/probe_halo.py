@@ -1,4 +1,4 @@
-"""Where the big halo tile's main loop spends its time (measurement builds, mg_set_option(10, v); tools/probe_halo.py):
+"""Where the big halo tile's main loop spends its time (measurement builds, OPT_PROBE_HALO_VARIANT = v; tools/probe_halo.py):
    1 main loop only | 2 ... without the weight stream | 3 ... without s_barrier | 4 s_memtime stamps per wave:
    cycles parked in the vmcnt wait, in s_barrier, and from the barrier to the end of the tap's MFMA issue."""
 import os, sys
@@ -32,10 +32,11 @@ for name, cin, cout, hw, spade in SHAPES:
         flops = 2.0 * n * hw * hw * cout * cin * 9
         taps = cin // 32 * 9
     res = {}
-    with torch.no_grad():
+    touched = (_cabi.OPT_PROBE_NOXPRE, _cabi.OPT_PROBE_HALO_VARIANT, _cabi.OPT_CONV_HALO_BIG, _cabi.OPT_PROBE_ADDR_LO, _cabi.OPT_PROBE_ADDR_HI)
+    with torch.no_grad(), _cabi.options({k: _cabi.get_option(k) for k in touched}):      # everything set below is put back on the way out
         for rep in range(2):
             for pr in (1,):
-                be.mg_set_option(15, pr); be.mg_set_option(10, 0)
+                be.mg_set_option(_cabi.OPT_PROBE_NOXPRE, pr); be.mg_set_option(_cabi.OPT_PROBE_HALO_VARIANT, 0)
                 for _ in range(3): fn()
                 torch.cuda.synchronize()
                 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -43,8 +44,8 @@ for name, cin, cout, hw, spade in SHAPES:
                 for _ in range(10): fn()
                 e.record(); torch.cuda.synchronize()
                 res.setdefault(f"prio{pr}", []).append(s.elapsed_time(e) / 10)
-            be.mg_set_option(15, 0)
-            be.mg_set_option(4, 0)
+            be.mg_set_option(_cabi.OPT_PROBE_NOXPRE, 0)
+            be.mg_set_option(_cabi.OPT_CONV_HALO_BIG, 0)
             for _ in range(3): fn()
             torch.cuda.synchronize()
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -52,9 +53,9 @@ for name, cin, cout, hw, spade in SHAPES:
             for _ in range(10): fn()
             e.record(); torch.cuda.synchronize()
             res.setdefault("small", []).append(s.elapsed_time(e) / 10)
-            be.mg_set_option(4, 1)
+            be.mg_set_option(_cabi.OPT_CONV_HALO_BIG, 1)
             for mode in ((0, 1) if spade else (0, 1, 2, 3, 4)):
-                be.mg_set_option(10, mode)
+                be.mg_set_option(_cabi.OPT_PROBE_HALO_VARIANT, mode)
                 for _ in range(3): fn()
                 torch.cuda.synchronize()
                 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -62,21 +63,19 @@ for name, cin, cout, hw, spade in SHAPES:
                 for _ in range(10): fn()
                 e.record(); torch.cuda.synchronize()
                 res.setdefault(mode, []).append(s.elapsed_time(e) / 10)
-        be.mg_set_option(10, 1 if spade else 4)
+        be.mg_set_option(_cabi.OPT_PROBE_HALO_VARIANT, 1 if spade else 4)
         out = fn(); torch.cuda.synchronize()
         probe = torch.zeros(nwg_of(n, hw, cout, spade) * 80, dtype=torch.int64, device="cuda")
         a = probe.data_ptr()
         s32 = lambda v: v - (1 << 32) if v >= (1 << 31) else v
-        be.mg_set_option(13, s32(a & 0xffffffff)); be.mg_set_option(14, s32(a >> 32))
+        be.mg_set_option(_cabi.OPT_PROBE_ADDR_LO, s32(a & 0xffffffff)); be.mg_set_option(_cabi.OPT_PROBE_ADDR_HI, s32(a >> 32))
         eps = {}
         for mode in (5, 6, 7):
-            be.mg_set_option(15, 1 if mode == 7 else 0)
-            be.mg_set_option(10, 5 if mode == 7 else mode)
+            be.mg_set_option(_cabi.OPT_PROBE_NOXPRE, 1 if mode == 7 else 0)
+            be.mg_set_option(_cabi.OPT_PROBE_HALO_VARIANT, 5 if mode == 7 else mode)
             for _ in range(2): fn()
             torch.cuda.synchronize()
             eps[mode] = probe.view(-1, 4, 20).cpu().numpy().copy()
-        be.mg_set_option(10, 0); be.mg_set_option(15, 0)
-        be.mg_set_option(13, 0); be.mg_set_option(14, 0)
     t = {m: min(v) * 1e3 for m, v in res.items()}
     for m in (2, 3, 4): t.setdefault(m, float('nan'))
     print(f"{name:24s} full {t[0]:7.1f} us {flops/t[0]/1e6:6.0f} TF/s | main loop {t[1]:7.1f} us {flops/t[1]/1e6:6.0f} TF/s"

@@ -1,4 +1,4 @@
-"""Where a stage of wgrad3x3_kernel<2, 2> goes (stamped build, mg_set_option(12, 1); tools/probe_wgrad3x3.py):
+"""Where a stage of wgrad3x3_kernel<2, 2> goes (stamped build, OPT_PROBE_WGRAD3X3 = 1; tools/probe_wgrad3x3.py):
 s_memrealtime ticks (10 ns) per stage and wave in the vmcnt wait, the barrier, the DMA issue (with its address arithmetic)
 and the ds_read + MFMA block; K-loop and atomics-epilogue time per workgroup."""
 import os, sys
@@ -19,20 +19,20 @@ for name, cin, cout, hw in (("x 128ch, dy 256ch @512", 128, 256, 512), ("x 128ch
     flops = 2.0 * n * hw * hw * cin * cout * 9
     res = {}
     for mode in (0, 1):
-        be.mg_set_option(12, mode)
-        for _ in range(2): fn()
-        torch.cuda.synchronize()
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        for _ in range(5): fn()
-        e.record(); torch.cuda.synchronize()
+        with _cabi.options({_cabi.OPT_PROBE_WGRAD3X3: mode}):
+            for _ in range(2): fn()
+            torch.cuda.synchronize()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(5): fn()
+            e.record(); torch.cuda.synchronize()
         res[mode] = s.elapsed_time(e) / 5
     probe = torch.zeros(1 << 20, dtype=torch.int64, device="cuda")
     a = probe.data_ptr()
     s32 = lambda v: v - (1 << 32) if v >= (1 << 31) else v
-    be.mg_set_option(13, s32(a & 0xffffffff)); be.mg_set_option(14, s32(a >> 32))
-    be.mg_set_option(12, 1); fn(); torch.cuda.synchronize(); be.mg_set_option(12, 0)
-    be.mg_set_option(13, 0); be.mg_set_option(14, 0)
+    # low half first: setting the high half hands the address over (and, on the way out, the null address again)
+    with _cabi.options({_cabi.OPT_PROBE_ADDR_LO: s32(a & 0xffffffff), _cabi.OPT_PROBE_ADDR_HI: s32(a >> 32), _cabi.OPT_PROBE_WGRAD3X3: 1}):
+        fn(); torch.cuda.synchronize()
     st = probe.view(-1, 8).cpu().numpy()
     st = st[st[:, 6] > 0].astype(np.float64)
     nk = st[:, 6]

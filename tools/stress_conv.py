@@ -17,7 +17,8 @@ if not use_bias:
     ref = ref - b
     b = None
 THR = 2e-3 if DT == torch.float32 else 0.06
-for name, opts in (("halo8", {2: 1, 4: 0}), ("halo16", {2: 1, 4: 1}), ("generic", {2: 0, 4: 0})):
+HALO, BIG = _cabi.OPT_CONV_HALO, _cabi.OPT_CONV_HALO_BIG
+for name, opts in (("halo8", {HALO: 1, BIG: 0}), ("halo16", {HALO: 1, BIG: 1}), ("generic", {HALO: 0, BIG: 0})):
     for k, v in opts.items():
         try: _cabi.backend().mg_set_option(k, v)
         except RuntimeError as e: print('option not supported', k)

@@ -52,10 +52,9 @@ def timed(fn, d, reps=4):
     for _ in range(reps): fn(d, st)
     e.record(); torch.cuda.synchronize()
     return s.elapsed_time(e) / reps
-CONV_VARIANTS = [("default", ()), ("no halo (2,0)", ((2, 0, 1),)), ("halo 8x16 tiles (4,0)", ((4, 0, 1),)), ("no 256x256 tiles (1,0)", ((1, 0, 1),)),
-                 ("no split-K (5,0)", ((5, 0, 1),)), ("wide split-K (17,1)", ((17, 1, 0),)), ("ring 4 (9,4)", ((9, 4, 3),)),
-                 ("no thin (6,0)", ((6, 0, 2),)), ("no dot (8,0)", ((8, 0, 1),))]
-WG_VARIANTS = [("default", (), None), ("no wgrad3x3 (3,0)", ((3, 0, 1),), None), ("no thin (6,0)", ((6, 0, 2),), None)]
+CONV_VARIANTS = [("default", {}), ("no halo (2,0)", {2: 0}), ("halo 8x16 tiles (4,0)", {4: 0}), ("no 256x256 tiles (1,0)", {1: 0}),
+                 ("no split-K (5,0)", {5: 0}), ("no thin (6,0)", {6: 0}), ("no dot (8,0)", {8: 0})]
+WG_VARIANTS = [("default", {}, None), ("no wgrad3x3 (3,0)", {3: 0}, None), ("no thin (6,0)", {6: 0}, None)]
 rows, gain_tot, base_tot = [], 0.0, 0.0
 for (kind, k), ds in groups.items():
     d = ds[0]; fn = orig_conv if kind == "conv" else orig_wg
@@ -65,19 +64,18 @@ for (kind, k), ds in groups.items():
         variants = [(n, o, None) for n, o in CONV_VARIANTS]
     else:
         desc = f"wgrad N{kd['N']} x{kd['Hin']}x{kd['Win']}x{kd['Cin']} dy{kd['Hj']}x{kd['Wj']}x{kd['Cg']} t{kd['ntaps']} s{kd['isy']}"
-        variants = list(WG_VARIANTS) + [(f"splitk {s}", (), s) for s in (2, 4, 8, 16, 32, 64, 128)]
+        variants = list(WG_VARIANTS) + [(f"splitk {s}", {}, s) for s in (2, 4, 8, 16, 32, 64, 128)]
     def run(opts, splitk, reps):
-        for key, v, _ in opts: be.mg_set_option(key, v)
         old = getattr(d, "splitk", None)
         if splitk is not None: d.splitk = splitk
-        try:
-            ms = timed(fn, d, reps)
-        except Exception:                             # a variant the shape does not support
-            ms = float("inf")
+        with C.options(opts, be):
+            try:
+                ms = timed(fn, d, reps)
+            except Exception:                         # a variant the shape does not support
+                ms = float("inf")
         if splitk is not None: d.splitk = old
-        for key, _, dv in opts: be.mg_set_option(key, dv)
         return ms
-    base = run((), None, 8)
+    base = run({}, None, 8)
     base_tot += base * len(ds)
     best = None
     for name, opts, splitk in variants[1:]:
@@ -85,7 +83,7 @@ for (kind, k), ds in groups.items():
         if v1 > 0.96 * base:
             continue
         # candidate: interleave default / variant twice more; a win must hold against the FASTEST default and by the SLOWEST variant run
-        d2, v2, d3, v3 = run((), None, 8), run(opts, splitk, 8), run((), None, 8), run(opts, splitk, 8)
+        d2, v2, d3, v3 = run({}, None, 8), run(opts, splitk, 8), run({}, None, 8), run(opts, splitk, 8)
         dmin, vmax = min(base, d2, d3), max(v1, v2, v3)
         if vmax < 0.96 * dmin and (best is None or vmax < best[0]):
             best = (vmax, name, dmin)
