@@ -167,7 +167,7 @@ class SpectralPlan:
             else:
                 dtype, rows_p, cols_p, mode = g
                 row.dst, row.mode, row.rows_p, row.cols_p = ip + off, mode, rows_p, cols_p
-                row.dtype = C.MG_BF16 if dtype == torch.bfloat16 else C.MG_F32
+                row.dtype = ops._dtype_code(dtype)
             row.first_block = first
             first += cnt
         be.mg_pack_weights(table.upload(), len(jobs), ops._p(bmap), first, stream)

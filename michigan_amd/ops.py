@@ -84,12 +84,16 @@ def _sync_bn_all_reduce(t: torch.Tensor, kind: str):
 STATS_FROM_UPSAMPLE_SOURCE = True     # batch statistics of a 2x-upsampled tensor from its quarter-size source (A/B: tools/ab_pyflag.py)
 
 
-def _dt(t: torch.Tensor) -> int:
-    if t.dtype == torch.bfloat16:
+def _dtype_code(dtype) -> int:
+    if dtype == torch.bfloat16:
         return C.MG_BF16
-    if t.dtype == torch.float32:
+    if dtype == torch.float32:
         return C.MG_F32
-    raise TypeError(f"michigan_amd kernels compute in bfloat16 or float32, got {t.dtype}")
+    raise TypeError(f"michigan_amd kernels compute in bfloat16 or float32, got {dtype}")
+
+
+def _dt(t: torch.Tensor) -> int:
+    return _dtype_code(t.dtype)
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -177,6 +181,69 @@ def _launch_conv(inp, wt, out, bias, taps, *, Hj, Wj, isy, isx, osy=1, osx=1, oo
     C.backend().mg_conv_taps(d, _stream(inp))
 
 
+def _arena_epoch(p) -> int:
+    """Update count of the flat optimiser arena a parameter lives in (optim.FlatAdam tags its parameters with
+    `_mg_arena`); 0 for parameters torch updates itself (their version counter moves instead)."""
+    arena = getattr(p, "_mg_arena", None)
+    return 0 if arena is None else arena.weight_epoch
+
+
+def _param_state(params):
+    """What a tensor derived from `params` is valid for: per parameter, its autograd version counter and its arena's update count."""
+    return [(p._version, _arena_epoch(p)) for p in params]
+
+
+class _ParamCache:
+    """Derived tensors of parameters, each valid until one of its source parameters changes.  An entry is keyed by the parameters'
+    addresses (+ whatever else the caller puts into the key) and stamped with _param_state; it holds the parameters by weak reference."""
+    PRUNE_ABOVE = 4096
+
+    def __init__(self):
+        self._entries = {}                 # key -> [state, weak references of the parameters, value]
+
+    def get(self, key, params):
+        """The value stored for these very parameters in their current state, or None."""
+        ent = self._entries.get(key)
+        if ent is None:
+            return None
+        for ref, (version, epoch), p in zip(ent[1], ent[0], params):
+            # identity through weak references: a freed parameter's address (and version 0) can be re-used by a new one
+            if ref() is not p or p._version != version or _arena_epoch(p) != epoch:
+                return None
+        return ent[2]
+
+    def only_epoch_moved(self, key, params) -> bool:
+        """Is there an entry that is stale ONLY because an arena's update count moved (the optimiser stepped), not a tensor version?"""
+        ent = self._entries.get(key)
+        return ent is not None and all(ref() is p and p._version == version for ref, (version, _), p in zip(ent[1], ent[0], params))
+
+    def put(self, key, params, value):
+        if len(self._entries) > self.PRUNE_ABOVE:
+            self.prune()
+        self._entries[key] = [_param_state(params), tuple(weakref.ref(p) for p in params), value]
+
+    def restamp(self, key):
+        """The value of this entry was refreshed in place: it is valid for its parameters' current state."""
+        ent = self._entries[key]
+        ent[0] = _param_state([ref() for ref in ent[1]])
+
+    def live(self, arena):
+        """(key, parameters, value) of every entry whose parameters are alive and whose first one lives in `arena`."""
+        for key, (_, refs, value) in list(self._entries.items()):
+            params = [ref() for ref in refs]
+            if all(p is not None for p in params) and getattr(params[0], "_mg_arena", None) is arena:
+                yield key, params, value
+
+    def prune(self):
+        """Drop the entries of parameters that no longer exist."""
+        for key in [k for k, ent in self._entries.items() if any(ref() is None for ref in ent[1])]:
+            del self._entries[key]
+
+
+_PACK_CACHE = _ParamCache()           # pack_weight: (addresses, dtype, rows_p, cols_p, mode) -> GEMM image
+_BIAS_PAIR_CACHE = _ParamCache()      # spade_bias_rows: (address of mlp_gamma.bias, of mlp_beta.bias) -> interleaved rows
+
+
 def pack_weight(w0: torch.Tensor, w1: Optional[torch.Tensor], dtype, rows_p: int, cols_p: int, mode: int) -> torch.Tensor:
     """Reference-layout fp32 weight(s) [Cout, Cin, kh, kw] -> GEMM image [taps, rows_p, cols_p] in `dtype`
     (one HIP launch: permute + zero-pad + cast; two tensors = fused SPADE gamma/beta row interleave).
@@ -199,35 +266,28 @@ def pack_weight(w0: torch.Tensor, w1: Optional[torch.Tensor], dtype, rows_p: int
         if geoms is None:
             geoms = origin._mg_pack_geom = set()
         geoms.add((dtype, rows_p, cols_p, mode))
-    slot = None
+    key = None
     if isinstance(w0, torch.nn.Parameter) and (w1 is None or isinstance(w1, torch.nn.Parameter)):
-        slot = (w0.data_ptr(), 0 if w1 is None else w1.data_ptr(), dtype, rows_p, cols_p, mode)
-        state = (w0._version, 0 if w1 is None else w1._version, _arena_epoch(w0), 0 if w1 is None else _arena_epoch(w1))
-        hit = _PACK_CACHE.get(slot)
-        # identity through weak references: a freed parameter's address (and version 0) can be re-used by a new one
-        if hit is not None and hit[1]() is w0 and (w1 is None or hit[2]() is w1):
-            if hit[0] == state:
-                return hit[3]
-            arena = getattr(w0, "_mg_arena", None)
-            if BATCHED_PACK and arena is not None and hit[0][:2] == state[:2] and (w1 is None or getattr(w1, "_mg_arena", None) is arena):
-                _repack_arena(arena)                    # the optimiser stepped: refresh every image of this arena in ONE launch
-                hit = _PACK_CACHE.get(slot)
-                if hit is not None and hit[0] == state:
-                    return hit[3]
-    dst = _pack_weight(w0, w1, dtype, rows_p, cols_p, mode)
-    if slot is not None:
-        if len(_PACK_CACHE) > 4096:                                  # slots of parameters that no longer exist
-            for k in [k for k, v in _PACK_CACHE.items() if v[1]() is None]:
-                del _PACK_CACHE[k]
-        _PACK_CACHE[slot] = (state, weakref.ref(w0), None if w1 is None else weakref.ref(w1), dst)   # one image per slot: a stale one is replaced
+        params = (w0,) if w1 is None else (w0, w1)
+        key = (w0.data_ptr(), 0 if w1 is None else w1.data_ptr(), dtype, rows_p, cols_p, mode)
+        hit = _PACK_CACHE.get(key, params)
         arena = getattr(w0, "_mg_arena", None)
+        if (hit is None and BATCHED_PACK and arena is not None and (w1 is None or getattr(w1, "_mg_arena", None) is arena)
+                and _PACK_CACHE.only_epoch_moved(key, params)):
+            _repack_arena(arena)                        # the optimiser stepped: refresh every image of this arena in ONE launch
+            hit = _PACK_CACHE.get(key, params)
+        if hit is not None:
+            return hit
+    dst = _pack_weight(w0, w1, dtype, rows_p, cols_p, mode)
+    if key is not None:
+        _PACK_CACHE.put(key, params, dst)               # one image per slot: a stale one is replaced
         if arena is not None:
-            _ARENA_PACK_TABLES.pop(id(arena), None)                  # the arena's job table has to learn about this slot
+            drop_arena_pack_table(arena)                # the arena's job table has to learn about this slot
     return dst
 
 
 BATCHED_PACK = True          # refresh all packed images of an optimiser arena with one mg_pack_weights launch (False: per-layer mg_pack_weight, as for parameters outside an arena; tests)
-_ARENA_PACK_TABLES = {}      # id(arena) -> (weakref(arena), slots, job table (device), block map (device), nblocks)
+_ARENA_PACK_TABLES = weakref.WeakKeyDictionary()     # arena -> (weak references of the parameters, cache keys, job table, block map (device), nblocks, table address)
 
 
 class DeviceTable:
@@ -265,55 +325,40 @@ def _repack_arena(arena):
     """Re-pack every cached GEMM image whose source parameters live in `arena` with one batched launch (in place: the
     images keep their addresses) and stamp them with the parameters' current state.  The table holds only weak references
     to the parameters (they reference the arena, which must be able to die)."""
-    ent = _ARENA_PACK_TABLES.get(id(arena))
-    if ent is not None and (ent[0]() is not arena or any(r0() is None or (r1 is not None and r1() is None) for _, r0, r1, _ in ent[1])):
+    ent = _ARENA_PACK_TABLES.get(arena)
+    if ent is not None and any(ref() is None for ref in ent[0]):
         ent = None
     if ent is None:
-        for k in [k for k, v in _ARENA_PACK_TABLES.items() if v[0]() is None]:
-            del _ARENA_PACK_TABLES[k]
-        slots = []
-        for key, (state, r0, r1, dst) in _PACK_CACHE.items():
-            w0, w1 = r0(), (r1() if r1 is not None else None)
-            if w0 is None or getattr(w0, "_mg_arena", None) is not arena or (r1 is not None and w1 is None):
-                continue
-            if w0.shape[2] * w0.shape[3] <= 49:
-                slots.append((key, r0, r1, dst))
-        if not slots:
+        jobs = [job for job in _PACK_CACHE.live(arena) if job[1][0].shape[2] * job[1][0].shape[3] <= 49]
+        if not jobs:
             return
         be = C.backend()
-        dev = slots[0][3].device
+        dev = jobs[0][2].device
         counts = []
-        table = DeviceTable(C.PackJob, len(slots), dev)
+        table = DeviceTable(C.PackJob, len(jobs), dev)
         first = 0
-        for row, (key, r0, r1, dst) in zip(table.begin_update(), slots):
-            w0, w1 = r0(), (r1() if r1 is not None else None)
+        for row, (key, params, dst) in zip(table.begin_update(), jobs):
+            w0, w1 = params[0], (params[1] if len(params) > 1 else None)
             _, _, dtype, rows_p, cols_p, mode = key
             taps = w0.shape[2] * w0.shape[3]
             nb = int(be.mg_pack_job_blocks(mode, w0.shape[0], w0.shape[1], taps, rows_p, cols_p))
             row.w0, row.w1, row.dst, row.sigma = w0.data_ptr(), (w1.data_ptr() if w1 is not None else None), dst.data_ptr(), None
-            row.dtype = C.MG_BF16 if dtype == torch.bfloat16 else C.MG_F32
+            row.dtype = _dtype_code(dtype)
             row.cout, row.cin, row.taps = w0.shape[0], w0.shape[1], taps
             row.rows_p, row.cols_p, row.mode, row.first_block = rows_p, cols_p, mode, first
             counts.append(nb)
             first += nb
-        ent = (weakref.ref(arena), slots, table, block_map(counts, dev), first, table.upload())
-        _ARENA_PACK_TABLES[id(arena)] = ent
-    _, slots, table, bmap, nblocks, tab_ptr = ent
-    C.backend().mg_pack_weights(tab_ptr, len(slots), _p(bmap), nblocks, _stream(bmap))
-    for key, r0, r1, dst in slots:
-        w0, w1 = r0(), (r1() if r1 is not None else None)
-        state = (w0._version, 0 if w1 is None else w1._version, _arena_epoch(w0), 0 if w1 is None else _arena_epoch(w1))
-        _PACK_CACHE[key] = (state, r0, r1, dst)
+        refs = [weakref.ref(p) for _, params, _ in jobs for p in params]
+        ent = _ARENA_PACK_TABLES[arena] = (refs, [key for key, _, _ in jobs], table, block_map(counts, dev), first, table.upload())
+    _, keys, table, bmap, nblocks, tab_ptr = ent
+    C.backend().mg_pack_weights(tab_ptr, len(keys), _p(bmap), nblocks, _stream(bmap))
+    for key in keys:
+        _PACK_CACHE.restamp(key)
 
 
-_PACK_CACHE = {}
-
-
-def _arena_epoch(p) -> int:
-    """Update count of the flat optimiser arena a parameter lives in (optim.FlatAdam tags its parameters with
-    `_mg_arena`); 0 for parameters torch updates itself (their version counter moves instead)."""
-    arena = getattr(p, "_mg_arena", None)
-    return 0 if arena is None else arena.weight_epoch
+def drop_arena_pack_table(arena):
+    """Forget the batched re-pack's job table of `arena`: the set of cached images changed, or the parameters' storage moved."""
+    _ARENA_PACK_TABLES.pop(arena, None)
 
 
 def _pack_weight(w0, w1, dtype, rows_p, cols_p, mode):
@@ -322,7 +367,7 @@ def _pack_weight(w0, w1, dtype, rows_p, cols_p, mode):
         w1 = w1.detach().float().contiguous()
     cout, cin, kh, kw = w0.shape
     dst = torch.empty((kh * kw, rows_p, cols_p), dtype=dtype, device=w0.device)
-    C.backend().mg_pack_weight(_p(w0), _p(w1), _p(dst), C.MG_BF16 if dtype == torch.bfloat16 else C.MG_F32,
+    C.backend().mg_pack_weight(_p(w0), _p(w1), _p(dst), _dtype_code(dtype),
                                cout, cin, kh * kw, rows_p, cols_p, mode, _stream(w0))
     return dst
 
@@ -364,7 +409,7 @@ def _grad_premasked(dh: torch.Tensor, h: torch.Tensor, act: int) -> bool:
     reset_mask_protocol() (every optimiser zero_grad / trainer step) drops whatever an interrupted backward left behind."""
     if act not in (ACT_RELU, ACT_LRELU):
         return False
-    hit = _RELU_MASKED.pop(dh.data_ptr(), None) == (h.data_ptr(), dh._version)
+    hit = _take_mask_record(dh, h)
     if act == ACT_LRELU and h.data_ptr() in _FOLD_EXPECTED:
         _FOLD_EXPECTED.pop(h.data_ptr(), None)
         if MASK_PROTOCOL_CHECK and not hit and FUSE_LRELU_MASK and FUSE_RELU_MASK:
@@ -387,7 +432,6 @@ def expire_fold_expectations():
 
 
 def _weak_node(t):
-    import weakref
     try:
         return weakref.ref(t.grad_fn) if t.grad_fn is not None else None
     except TypeError:                                      # a node type without weak-reference support: the entry expires at the next forward
@@ -404,6 +448,24 @@ _RELU_MASKED = {}       # address of a ReLU-masked data gradient -> (address of 
 _FOLD_EXPECTED = {}     # address of a LeakyReLU output whose (single) consumer committed to the mask fold at forward time -> weakref of its producer node
 _DGRAD_CLASSES = {}     # (kh, kw, stride, pad) -> [(py, px, taps, (lo, hi))], tap order of the class-sorted weight image
 _DGRAD_PERM = {}        # (kh, kw, stride, pad, device) -> index tensor that sorts the packed taps by parity class
+
+
+def _leave_mask_record(g: torch.Tensor, y: torch.Tensor):
+    """The gradient buffer `g` already carries the backward mask of the activation output `y`."""
+    # g is already multiplied by the ReLU mask of the tensor the forward conv consumed (conv_dgrad's epilogue, the max-pool backward,
+    # _ActTapFn); the producer of that tensor finds the record below and skips its activation-backward pass.  The record is keyed
+    # by g's address and carries its version counter: a gradient that autograd summed out of place lives elsewhere, one it
+    # accumulated in place has a bumped version -- in both cases the producer masks again (harmless: idempotent
+    # for ReLU), so a skip can only happen for the very buffer that launch wrote.
+    # mask_slope > 0 (LeakyReLU): masking twice is NOT harmless, so only tensors whose producer declared the conv their
+    # single consumer are folded (mark_single_consumer_lrelu) -- then the buffer reaches the producer untouched and the
+    # record is always found (MG_MASK_PROTOCOL_CHECK=1 makes the producer raise if it is not).
+    _RELU_MASKED[g.data_ptr()] = (y.data_ptr(), g._version)
+
+
+def _take_mask_record(g: torch.Tensor, y: torch.Tensor) -> bool:
+    """Remove whatever record there is for the buffer `g`; True when it says that `g`, as it is now, carries the mask of `y`."""
+    return _RELU_MASKED.pop(g.data_ptr(), None) == (y.data_ptr(), g._version)
 
 
 def _dgrad_classes(kh: int, kw: int, stride: int, pad: int):
@@ -454,27 +516,20 @@ def conv_dgrad(dy: torch.Tensor, wt: torch.Tensor, kh: int, kw: int, stride: int
         _launch_conv(dy, wt[lo:hi], dx, None, taps, Hj=hj, Wj=wj, isy=1, isx=1,
                      osy=stride, osx=stride, ooy=py, oox=px, cout=cin, cout_gemm=cin, relu_mask=relu_mask, mask_slope=mask_slope)
     if relu_mask is not None:
-        # dx is already multiplied by the ReLU mask of the tensor the forward conv consumed; the producer of that
-        # tensor finds the record below and skips its activation-backward pass.  The record is keyed by dx's address
-        # and carries its version counter: a gradient that autograd summed out of place lives elsewhere, one it
-        # accumulated in place has a bumped version -- in both cases the producer masks again (harmless: idempotent
-        # for ReLU), so a skip can only happen for the very buffer this launch wrote.
-        # mask_slope > 0 (LeakyReLU): masking twice is NOT harmless, so only tensors whose producer declared this conv their
-        # single consumer are folded (mark_single_consumer_lrelu) -- then the buffer reaches the producer untouched and the
-        # record is always found (MG_MASK_PROTOCOL_CHECK=1 makes the producer raise if it is not).
         assert relu_mask.shape == dx.shape and relu_mask.dtype == dx.dtype
-        _RELU_MASKED[dx.data_ptr()] = (relu_mask.data_ptr(), dx._version)
+        _leave_mask_record(dx, relu_mask)
     return dx
 
 
-def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, kh: int, kw: int, stride: int, pad: int, want_bias: bool = False, out=None):
+def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, kh: int, kw: int, stride: int, pad: int, want_bias: bool = False, out=None, beside: bool = False):
     """dW in GEMM order [T, Cg8, Cin] (fp32) of a forward conv; split-K over pixels, fp32 atomics.
     want_bias=True also returns the bias gradient [Cg8] (column sums of dy) from the same launch.
-    out = (dw, dbias): accumulate into these existing buffers (the optimiser's GEMM-order arena) instead."""
+    out = (dw, dbias): accumulate into these existing buffers (the optimiser's GEMM-order arena) instead;
+    beside (with out): the launch runs beside another stream's work, the 3x3 kernel keeps to one workgroup per CU (mg_wgrad_desc.flags bit 1)."""
     n, h, w, cin = x.shape
     _, hj, wj, cg8 = dy.shape
     if out is not None:
-        return _wgrad_launch(x, dy, fwd_taps(kh, kw, pad), stride, want_bias, out)
+        return _wgrad_launch(x, dy, fwd_taps(kh, kw, pad), stride, want_bias, out, beside)
     if _wgrad_swapped(stride, cg8, cin):
         # Few output channels (conv_img, the discriminators' 1-channel heads): a 128-row tile would be 94 % padding.
         # dW[t][co][ci] = sum_q x[q][ci] * dy[q + (pad - k_t)][co] is the weight gradient of the mirrored problem with
@@ -501,8 +556,7 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, kh: int, kw: int, stride: int,
 # pass (+0.4 ms), the background encoder beside head_0 / G_middle_* (flat).  MG_WGRAD_STREAM=0 restores the single stream.
 WGRAD_SIDE_STREAM = os.environ.get("MG_WGRAD_STREAM", "1") != "0"
 WGRAD_HALF_CU = os.environ.get("MG_WGRAD_HALF_CU", "1") != "0"     # side-stream wgrad3x3 launches keep to one workgroup per CU (flags bit 1): -0.6 / -0.55 / 0.0 ms on three boxes
-_WGRAD_BESIDE = False
-_WGRAD_STREAMS = {}            # device index -> [stream, dirty, held]: held = [(event, x, dy, bytes)] of launches that may still be running
+_WGRAD_STREAMS = {}            # device index -> _SideStream
 # The held operands outlive their autograd nodes while the side queue lags (the case the stream is for): their bytes are BOUNDED -- past the
 # budget the main stream waits for the oldest launches' events and lets go of them.  At bs 8 / 512^2 the whole backward holds
 # < 3 GB this way (bench.py reports torch's peak for both settings of MG_WGRAD_STREAM under `extra.peak_memory_gb`).
@@ -566,10 +620,42 @@ def _new_side_stream(device):
 _REJECTED_STREAMS = []
 
 
-def _wgrad_side(device):
+class _SideStream:
+    """The second stream of one device and the weight-gradient launches that may still be running on it."""
+
+    def __init__(self, device):
+        self.stream = _new_side_stream(device)
+        self.dirty = False             # launches were issued to the stream since the current stream last joined it
+        self.held = []                 # [(event, x, dy, bytes)], oldest first
+
+    def hold(self, event, x, dy):
+        """Keep the operands of the launch that `event` ends referenced until it has finished, within WGRAD_HELD_BUDGET."""
+        # The operands stay REFERENCED until their launch has finished (or the main stream has joined).  That keeps their memory from
+        # being reused -- and it keeps autograd from accumulating into dy IN PLACE: a conv's dy is also the gradient of its residual
+        # input (returned as such by _ConvFn.backward), and the engine's input buffer adds the next incoming gradient into a tensor it
+        # holds the only reference to.  In stream order that write came after the wgrad's reads; beside a side stream it raced them
+        # (round 5: G_middle_1.conv_1's weight gradient at cosine 0.78 in tests/test_gpu_fullsize.py before this list existed).
+        held = self.held
+        while held and held[0][0].query():
+            held.pop(0)
+        held.append((event, x, dy, x.numel() * x.element_size() + dy.numel() * dy.element_size()))
+        over = sum(h[3] for h in held) - WGRAD_HELD_BUDGET
+        while over > 0 and len(held) > 1:                              # the main stream falls in behind the oldest launches: their operands are free again
+            old = held.pop(0)
+            torch.cuda.current_stream(x.device).wait_event(old[0])
+            over -= old[3]
+
+    def join(self):
+        """The current stream waits for everything issued to the side stream so far; nothing has to be held any longer."""
+        torch.cuda.current_stream(self.stream.device).wait_stream(self.stream)
+        self.dirty = False
+        self.held.clear()
+
+
+def _wgrad_side(device) -> _SideStream:
     ent = _WGRAD_STREAMS.get(device.index)
     if ent is None:
-        ent = _WGRAD_STREAMS[device.index] = [_new_side_stream(device), False, []]
+        ent = _WGRAD_STREAMS[device.index] = _SideStream(device)
     return ent
 
 
@@ -577,42 +663,23 @@ def wgrad_join(device=None):
     """The current stream waits for every weight-gradient launch issued to the side stream so far (no-op when none was).  Behind the
     join the operands may be freed or rewritten by the current stream again: the references held for them are dropped."""
     for idx, ent in _WGRAD_STREAMS.items():
-        if ent[1] and (device is None or device.index == idx):
-            torch.cuda.current_stream(ent[0].device).wait_stream(ent[0])
-            ent[1] = False
-            ent[2].clear()
+        if ent.dirty and (device is None or device.index == idx):
+            ent.join()
 
 
 def sink_wgrad(arena, slot, x, dy, kh, kw, stride, pad, need_b):
     """Weight gradient of one convolution into its slot of the optimiser's GEMM-order arena (+ the bucket bookkeeping)."""
     if WGRAD_SIDE_STREAM and x.is_cuda:
         ent = _wgrad_side(x.device)
-        side, held = ent[0], ent[2]
+        side = ent.stream
         side.wait_stream(torch.cuda.current_stream(x.device))          # dy (and x) were produced on the current stream
-        global _WGRAD_BESIDE
         with torch.cuda.stream(side):
-            _WGRAD_BESIDE = WGRAD_HALF_CU                              # mg_wgrad_desc.flags bit 1: one workgroup of the 3x3 kernel per CU
-            try:
-                conv_wgrad(x, dy, kh, kw, stride, pad, want_bias=need_b, out=(slot[1], slot[2]))
-            finally:
-                _WGRAD_BESIDE = False
+            conv_wgrad(x, dy, kh, kw, stride, pad, want_bias=need_b, out=(slot[1], slot[2]), beside=WGRAD_HALF_CU)
             arena.slot_written(slot[0])                                # a bucket all-reduce it triggers is ordered behind the side stream
             ev = torch.cuda.Event()
             ev.record(side)
-        ent[1] = True
-        # The operands stay REFERENCED until their launch has finished (or the main stream has joined).  That keeps their memory from
-        # being reused -- and it keeps autograd from accumulating into dy IN PLACE: a conv's dy is also the gradient of its residual
-        # input (returned as such by _ConvFn.backward), and the engine's input buffer adds the next incoming gradient into a tensor it
-        # holds the only reference to.  In stream order that write came after the wgrad's reads; beside a side stream it raced them
-        # (round 5: G_middle_1.conv_1's weight gradient at cosine 0.78 in tests/test_gpu_fullsize.py before this list existed).
-        while held and held[0][0].query():
-            held.pop(0)
-        held.append((ev, x, dy, x.numel() * x.element_size() + dy.numel() * dy.element_size()))
-        over = sum(h[3] for h in held) - WGRAD_HELD_BUDGET
-        while over > 0 and len(held) > 1:                              # the main stream falls in behind the oldest launches: their operands are free again
-            old = held.pop(0)
-            torch.cuda.current_stream(x.device).wait_event(old[0])
-            over -= old[3]
+        ent.dirty = True
+        ent.hold(ev, x, dy)
         return
     conv_wgrad(x, dy, kh, kw, stride, pad, want_bias=need_b, out=(slot[1], slot[2]))
     arena.slot_written(slot[0])
@@ -629,14 +696,14 @@ BRANCH_STREAMS = int(os.environ.get("MG_BRANCH_STREAMS", "2"))
 
 def side_stream(device):
     """The second stream of the step (shared with the weight gradients)."""
-    return _wgrad_side(device)[0]
+    return _wgrad_side(device).stream
 
 
 def _wgrad_swapped(stride: int, cg8: int, cin: int) -> bool:
     return stride == 1 and cg8 <= 8 and cin >= 32
 
 
-def _wgrad_launch(x, dy, taps, stride, want_bias, out=None):
+def _wgrad_launch(x, dy, taps, stride, want_bias, out=None, beside=False):
     n, h, w, cin = x.shape
     _, hj, wj, cg8 = dy.shape
     ndw = len(taps) * cg8 * cin
@@ -656,7 +723,7 @@ def _wgrad_launch(x, dy, taps, stride, want_bias, out=None):
     d.Hj, d.Wj, d.Cg = hj, wj, cg8
     d.isy = d.isx = stride
     d.splitk = 0
-    d.flags = (1 if (WGRAD_USE_TR and x.dtype == torch.bfloat16) else 0) | (2 if _WGRAD_BESIDE else 0)
+    d.flags = (1 if (WGRAD_USE_TR and x.dtype == torch.bfloat16) else 0) | (2 if beside else 0)
     _set_taps(d, taps)
     assert dy.dtype == x.dtype
     if WGRAD_DETERMINISTIC:
@@ -730,7 +797,7 @@ class _Conv2dFn(torch.autograd.Function):
         cout, cin, kh, kw = weight.shape
         cx = x.shape[3]
         dout = dout.contiguous()
-        if act == ACT_RELU and _RELU_MASKED.pop(dout.data_ptr(), None) == (out.data_ptr(), dout._version):
+        if act == ACT_RELU and _take_mask_record(dout, out):
             dpre = dout                                  # the consumer's dgrad epilogue already applied this ReLU's mask
         else:
             dpre = act_backward(dout, out, act, slope)
@@ -946,10 +1013,7 @@ def _count_collective(kind: str):
     parallel.COLLECTIVES[kind] += 1
 
 
-_BIAS_PAIR_CACHE = {}
-
-
-_BIAS_PLANS = {}        # id(arena) -> plan of ALL (mlp_gamma.bias, mlp_beta.bias) pairs living in that optimiser arena
+_BIAS_PLANS = weakref.WeakKeyDictionary()        # arena -> plan of ALL (mlp_gamma.bias, mlp_beta.bias) pairs living in that optimiser arena
 
 
 class _BiasPlan:
@@ -997,8 +1061,7 @@ class _BiasPlan:
         if self.mask is not None:
             rows = rows * self.mask
         for (bg, bb), (a, b) in zip(live, self.offsets):
-            state = (bg._version, bb._version, _arena_epoch(bg), _arena_epoch(bb))
-            _BIAS_PAIR_CACHE[(bg.data_ptr(), bb.data_ptr())] = (state, weakref.ref(bg), weakref.ref(bb), rows[a:b])
+            _BIAS_PAIR_CACHE.put((bg.data_ptr(), bb.data_ptr()), (bg, bb), rows[a:b])
         return True
 
 
@@ -1007,27 +1070,20 @@ def spade_bias_rows(bg: torch.Tensor, bb: torch.Tensor) -> torch.Tensor:
     optimiser arena's update count, like pack_weight); pairs that live in a FlatAdam arena are refreshed all at once (_BiasPlan)."""
     if not (isinstance(bg, torch.nn.Parameter) and isinstance(bb, torch.nn.Parameter)):
         return _interleave32(bg.detach().float(), bb.detach().float()).contiguous()
-    key = (bg.data_ptr(), bb.data_ptr())
-    state = (bg._version, bb._version, _arena_epoch(bg), _arena_epoch(bb))
-    hit = _BIAS_PAIR_CACHE.get(key)
-    if hit is not None and hit[0] == state and hit[1]() is bg and hit[2]() is bb:
-        return hit[3]
+    key, params = (bg.data_ptr(), bb.data_ptr()), (bg, bb)
+    hit = _BIAS_PAIR_CACHE.get(key, params)
+    if hit is not None:
+        return hit
     arena = getattr(bg, "_mg_arena", None)
     if arena is not None and getattr(bb, "_mg_arena", None) is arena and hasattr(arena, "_span_of") and BATCHED_PACK:
-        plan = _BIAS_PLANS.get(id(arena))
-        if plan is None or plan.arena() is not arena:
-            for k in [k for k, v in _BIAS_PLANS.items() if v.arena() is None]:
-                del _BIAS_PLANS[k]
-            plan = _BIAS_PLANS[id(arena)] = _BiasPlan(arena)
+        plan = _BIAS_PLANS.get(arena)
+        if plan is None:
+            plan = _BIAS_PLANS[arena] = _BiasPlan(arena)
         plan.register(bg, bb)
-        if len(_BIAS_PAIR_CACHE) > 1024:
-            _BIAS_PAIR_CACHE.clear()
         if plan.refresh():
-            return _BIAS_PAIR_CACHE[key][3]
+            return _BIAS_PAIR_CACHE.get(key, params)
     rows = _interleave32(bg.detach().float(), bb.detach().float()).contiguous()
-    if len(_BIAS_PAIR_CACHE) > 1024:
-        _BIAS_PAIR_CACHE.clear()
-    _BIAS_PAIR_CACHE[key] = (state, weakref.ref(bg), weakref.ref(bb), rows)
+    _BIAS_PAIR_CACHE.put(key, params, rows)
     return rows
 
 
@@ -1040,28 +1096,88 @@ def _interleave32(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return torch.stack([a.reshape(cr // 32, 32), b.reshape(cr // 32, 32)], dim=1).reshape(2 * cr)
 
 
+def _spade_branch_fwd(who, x, actv, wg, bg, wb, bb, mean, rstd, act, slope, need_g1, up=False):
+    """Forward launch of one gamma|beta branch of `who` (the public function, for the error text): (out, 1 + gamma or None).
+    `up`: x is the half-resolution source of the tensor that is modulated."""
+    n, h, w = actv.shape[:3]
+    c = x.shape[3]
+    if wg.shape != wb.shape or wg.shape[0] != c or wg.shape[1] != actv.shape[3]:
+        raise ValueError(f"{who}: mlp_gamma / mlp_beta weights have the wrong shape")
+    kh = wg.shape[2]
+    rows = 2 * _roundup(c, 32)
+    wp = pack_weight(wg, wb, x.dtype, _roundup(rows, 128), actv.shape[3], 0)
+    bias = spade_bias_rows(bg, bb)
+    out = torch.empty((n, h, w, c), dtype=x.dtype, device=x.device)
+    # (1 + gamma) is only needed by the backward pass: the no_grad generator forward of the
+    # discriminator step (pix2pix_model.py:376) does not write it
+    g1 = torch.empty_like(out) if need_g1 else None
+    _launch_conv(actv, wp, out, bias, fwd_taps(kh, kh, kh // 2), Hj=h, Wj=w, isy=1, isx=1, cout=c, cout_gemm=rows,
+                 act=act, slope=slope, spade_x=x, mean=mean, rstd=rstd, gamma_out=g1, x_up=up)
+    return out, g1
+
+
+def _spade_branch_reduce(dh, h, g1, x, mean, rstd, act, slope, sums, up=False):
+    """Backward reduction of one branch: the gradient dgb of the gamma|beta conv's output and, into `sums` ([2, C] fp32), the two sums of the
+    batch-norm gradient.  Returns (dgb, the activation the apply pass still has to undo, h's pointer for it).  `up` (pair node only): x is the half-resolution source."""
+    n, hh, ww, c = dh.shape
+    p = n * hh * ww
+    rows = 2 * _roundup(c, 32)
+    be = C.backend()
+    alloc = torch.zeros if rows != 2 * c else torch.empty      # padded gamma/beta rows must read 0
+    dgb = alloc((n, hh, ww, rows), dtype=x.dtype, device=x.device)
+    ws = torch.empty(max(int(be.mg_stats_workspace(1, p, c)), 4), dtype=torch.uint8, device=x.device)
+    if _grad_premasked(dh, h, act):
+        act = ACT_NONE                               # conv_0 / conv_1's data-gradient epilogue already applied the LeakyReLU mask
+    hp = _p(h) if act != ACT_NONE else None          # the activation's output is only read for its sign
+    if up:
+        be.mg_norm_bwd_reduce_up(_p(dh), hp, _p(x), _p(g1), _dt(x), n, hh, ww, c, _p(mean), _p(rstd), act, slope,
+                                 _p(dgb), _p(sums), _p(ws), _stream(x))
+    else:
+        be.mg_norm_bwd_reduce(_p(dh), hp, _p(x), _p(g1), _dt(x), 1, p, c, _p(mean), _p(rstd), act, slope,
+                              _p(dgb), _p(sums), _p(ws), _stream(x))
+    return dgb, act, hp
+
+
+def _spade_branch_grads(needs, sink, actv, dgb, wg, wb, actv_relu):
+    """Gradients of one branch's (actv, w_gamma, b_gamma, w_beta, b_beta) from dgb; `needs`: which of the five are wanted.
+    What the optimiser's gradient sink takes (`sink` = (arena, leaf weight, b_gamma, b_beta)) comes back as None."""
+    hh, ww, rows = dgb.shape[1:]
+    c, kh = wg.shape[0], wg.shape[2]
+    pad = kh // 2
+    dactv = dwg = dbg = dwb = dbb = None
+    if needs[0]:
+        wt = pack_weight(wg, wb, dgb.dtype, _roundup(actv.shape[3], 128), rows, 1)
+        dactv = conv_dgrad(dgb, wt, kh, kh, 1, pad, (hh, ww), actv.shape[3],
+                           relu_mask=actv if (actv_relu and FUSE_RELU_MASK) else None)      # mlp_shared's ReLU (normalization.py:94-99)
+    need_w = needs[1] or needs[3]
+    need_b = needs[2] or needs[4]
+    slot = db = None
+    if sink is not None and needs[1] and needs[3]:
+        slot = sink[0].grad_slot(wg, wb, sink[2] if need_b else None, sink[3] if need_b else None, kh * kh, rows, actv.shape[3], None)
+    if slot is not None:
+        sink_wgrad(sink[0], slot, actv, dgb, kh, kh, 1, pad, need_b)
+    elif need_w:
+        res = conv_wgrad(actv, dgb, kh, kh, 1, pad, want_bias=need_b)
+        dwg, dwb = unpack_wgrad(res[0] if need_b else res, wg.shape, two=True)
+        db = res[1] if need_b else None
+    elif need_b:
+        db = channel_sums(dgb)[0, 0].float()
+    if db is not None:
+        db = db.reshape(rows // 64, 2, 32)
+        dbg, dbb = db[:, 0].reshape(-1)[:c], db[:, 1].reshape(-1)[:c]
+    return dactv, dwg, dbg, dwb, dbb
+
+
 class _SpadeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, actv, w_gamma, b_gamma, w_beta, b_beta, mean, rstd, count, act, slope, actv_relu=False, sink=None):
         ctx.actv_relu = bool(actv_relu)
         ctx.sink = sink
         x, actv = _nhwc(x), _nhwc(actv)
-        n, h, w, c = x.shape
         if actv.shape[:3] != x.shape[:3] or actv.dtype != x.dtype:
             raise ValueError("spade_modulate: activation map and x disagree in shape/dtype")
-        if w_gamma.shape != w_beta.shape or w_gamma.shape[0] != c or w_gamma.shape[1] != actv.shape[3]:
-            raise ValueError("spade_modulate: mlp_gamma / mlp_beta weights have the wrong shape")
-        kh = w_gamma.shape[2]
-        rows = 2 * _roundup(c, 32)
-        wp = pack_weight(w_gamma, w_beta, x.dtype, _roundup(rows, 128), actv.shape[3], 0)
-        bias = spade_bias_rows(b_gamma, b_beta)
-        out = torch.empty_like(x)
-        # (1 + gamma) is only needed by the backward pass: the no_grad generator forward of the
-        # discriminator step (pix2pix_model.py:376) does not write it
-        g1 = torch.empty_like(x) if any(ctx.needs_input_grad) else None
-        _launch_conv(actv, wp, out, bias, fwd_taps(kh, kh, kh // 2), Hj=h, Wj=w, isy=1, isx=1,
-                     cout=c, cout_gemm=rows, act=act, slope=slope,
-                     spade_x=x, mean=mean, rstd=rstd, gamma_out=g1)
+        out, g1 = _spade_branch_fwd("spade_modulate", x, actv, w_gamma, b_gamma, w_beta, b_beta, mean, rstd, act, slope,
+                                    any(ctx.needs_input_grad))
         if g1 is not None:
             ctx.save_for_backward(x, actv, w_gamma, w_beta, out, g1, mean, rstd)
         ctx.cfg = (count, act, slope)
@@ -1073,53 +1189,18 @@ class _SpadeFn(torch.autograd.Function):
         count, act, slope = ctx.cfg
         dh = dh.contiguous()
         n, hh, ww, c = x.shape
-        kh = w_gamma.shape[2]
-        pad = kh // 2
-        rows = 2 * _roundup(c, 32)
-        p = n * hh * ww
-        be = C.backend()
-        alloc = torch.zeros if rows != 2 * c else torch.empty      # padded gamma/beta rows must read 0
-        dgb = alloc((n, hh, ww, rows), dtype=x.dtype, device=x.device)
         sums = torch.empty((1, 2, c), dtype=torch.float32, device=x.device)
-        ws = torch.empty(max(int(be.mg_stats_workspace(1, p, c)), 4), dtype=torch.uint8, device=x.device)
-        if _grad_premasked(dh, h, act):
-            act = ACT_NONE                               # conv_0 / conv_1's data-gradient epilogue already applied the LeakyReLU mask
-        hp = _p(h) if act != ACT_NONE else None          # the activation's output is only read for its sign
-        be.mg_norm_bwd_reduce(_p(dh), hp, _p(x), _p(g1), _dt(x), 1, p, c, _p(mean), _p(rstd), act, slope,
-                              _p(dgb), _p(sums), _p(ws), _stream(x))
-        dx = dactv = dwg = dwb = dbg = dbb = None
-        work = None
+        dgb, act, hp = _spade_branch_reduce(dh, h, g1, x, mean, rstd, act, slope, sums)
+        dx = work = None
         if ctx.needs_input_grad[0] and SYNC_BN_GROUP is not None:
             work = _sync_bn_all_reduce(sums, "syncbn_bwd")    # overlaps with the gamma/beta conv's backward below
-        if ctx.needs_input_grad[1]:
-            wt = pack_weight(w_gamma, w_beta, x.dtype, _roundup(actv.shape[3], 128), rows, 1)
-            dactv = conv_dgrad(dgb, wt, kh, kh, 1, pad, (hh, ww), actv.shape[3],
-                               relu_mask=actv if (ctx.actv_relu and FUSE_RELU_MASK) else None)      # mlp_shared's ReLU (normalization.py:94-99)
-        need_w = ctx.needs_input_grad[2] or ctx.needs_input_grad[4]
-        need_b = ctx.needs_input_grad[3] or ctx.needs_input_grad[5]
-        db = None
-        slot = None
-        if ctx.sink is not None and need_w and ctx.needs_input_grad[2] and ctx.needs_input_grad[4]:
-            arena = ctx.sink[0]
-            slot = arena.grad_slot(w_gamma, w_beta, ctx.sink[2] if need_b else None, ctx.sink[3] if need_b else None,
-                                   kh * kh, rows, actv.shape[3], None)
-        if slot is not None:
-            sink_wgrad(arena, slot, actv, dgb, kh, kh, 1, pad, need_b)
-        elif need_w:
-            res = conv_wgrad(actv, dgb, kh, kh, 1, pad, want_bias=need_b)
-            dwg, dwb = unpack_wgrad(res[0] if need_b else res, w_gamma.shape, two=True)
-            db = res[1] if need_b else None
-        elif need_b:
-            db = channel_sums(dgb)[0, 0].float()
+        dactv, dwg, dbg, dwb, dbb = _spade_branch_grads(ctx.needs_input_grad[1:6], ctx.sink, actv, dgb, w_gamma, w_beta, ctx.actv_relu)
         if ctx.needs_input_grad[0]:
             if work is not None:
                 work.wait()
             dx = torch.empty_like(x)
-            be.mg_norm_bwd_apply(_p(dh), hp, _p(x), _p(g1), _dt(x), 1, p, c, _p(mean), _p(rstd),
-                                 _p(sums[0, 0]), _p(sums[0, 1]), 2 * c, 1.0 / float(count), act, slope, _p(dx), _stream(x))
-        if db is not None:
-            db = db.reshape(rows // 64, 2, 32)
-            dbg, dbb = db[:, 0].reshape(-1)[:c], db[:, 1].reshape(-1)[:c]
+            C.backend().mg_norm_bwd_apply(_p(dh), hp, _p(x), _p(g1), _dt(x), 1, n * hh * ww, c, _p(mean), _p(rstd),
+                                          _p(sums[0, 0]), _p(sums[0, 1]), 2 * c, 1.0 / float(count), act, slope, _p(dx), _stream(x))
         return dx, dactv, dwg, dbg, dwb, dbb, None, None, None, None, None, None, None
 
 
@@ -1137,91 +1218,44 @@ class _SpadePairFn(torch.autograd.Function):
         h, w = (2 * hs, 2 * ws) if up else (hs, ws)
         if actv0.shape[:3] != (n, h, w) or actv1.shape[:3] != (n, h, w) or actv0.dtype != x.dtype or actv1.dtype != x.dtype:
             raise ValueError("spade_modulate_pair: activation maps and x disagree in shape / dtype")
-        rows = 2 * _roundup(c, 32)
         need = any(ctx.needs_input_grad)
-        outs, g1s = [], []
-        for actv, wg, bg, wb, bb, act in ((actv0, wg0, bg0, wb0, bb0, act0), (actv1, wg1, bg1, wb1, bb1, act1)):
-            if wg.shape != wb.shape or wg.shape[0] != c or wg.shape[1] != actv.shape[3]:
-                raise ValueError("spade_modulate_pair: mlp_gamma / mlp_beta weights have the wrong shape")
-            kh = wg.shape[2]
-            wp = pack_weight(wg, wb, x.dtype, _roundup(rows, 128), actv.shape[3], 0)
-            bias = spade_bias_rows(bg, bb)
-            out = torch.empty((n, h, w, c), dtype=x.dtype, device=x.device)
-            g1 = torch.empty_like(out) if need else None
-            _launch_conv(actv, wp, out, bias, fwd_taps(kh, kh, kh // 2), Hj=h, Wj=w, isy=1, isx=1, cout=c, cout_gemm=rows,
-                         act=act, slope=slope, spade_x=x, mean=mean, rstd=rstd, gamma_out=g1, x_up=up)
-            outs.append(out)
-            g1s.append(g1)
+        (out0, g10), (out1, g11) = (_spade_branch_fwd("spade_modulate_pair", x, actv, wg, bg, wb, bb, mean, rstd, act, slope, need, up)
+                                    for actv, wg, bg, wb, bb, act in ((actv0, wg0, bg0, wb0, bb0, act0), (actv1, wg1, bg1, wb1, bb1, act1)))
         if need:
-            ctx.save_for_backward(x, actv0, wg0, wb0, outs[0], g1s[0], actv1, wg1, wb1, outs[1], g1s[1], mean, rstd)
+            ctx.save_for_backward(x, actv0, wg0, wb0, out0, g10, actv1, wg1, wb1, out1, g11, mean, rstd)
         ctx.cfg = (count, (act0, act1), slope, bool(up), (bool(relu0), bool(relu1)), sinks, (h, w))
-        return outs[0], outs[1]
+        return out0, out1
 
     @staticmethod
     def backward(ctx, dh0, dh1):
         x, actv0, wg0, wb0, h0, g10, actv1, wg1, wb1, h1, g11, mean, rstd = ctx.saved_tensors
         count, acts, slope, up, relus, sinks, (hh, ww) = ctx.cfg
         n, _, _, c = x.shape
-        p = n * hh * ww
-        rows = 2 * _roundup(c, 32)
-        be = C.backend()
         need_x = ctx.needs_input_grad[0]
         sums = torch.empty((2, 2, c), dtype=torch.float32, device=x.device)          # [branch][sum dxhat | sum dxhat * xhat][C]
         branches = ((dh0.contiguous(), h0, g10, actv0, wg0, wb0, 1), (dh1.contiguous(), h1, g11, actv1, wg1, wb1, 6))
-        acts = tuple(ACT_NONE if _grad_premasked(br[0], br[1], a) else a for br, a in zip(branches, acts))
-        dgbs = []
-        for b, (dh, h, g1, actv, wg, wb, base) in enumerate(branches):
-            alloc = torch.zeros if rows != 2 * c else torch.empty                      # padded gamma/beta rows must read 0
-            dgb = alloc((n, hh, ww, rows), dtype=x.dtype, device=x.device)
-            ws = torch.empty(max(int(be.mg_stats_workspace(1, p, c)), 4), dtype=torch.uint8, device=x.device)
-            hp = _p(h) if acts[b] != ACT_NONE else None
-            if up:
-                be.mg_norm_bwd_reduce_up(_p(dh), hp, _p(x), _p(g1), _dt(x), n, hh, ww, c, _p(mean), _p(rstd), acts[b], slope,
-                                         _p(dgb), _p(sums[b]), _p(ws), _stream(x))
-            else:
-                be.mg_norm_bwd_reduce(_p(dh), hp, _p(x), _p(g1), _dt(x), 1, p, c, _p(mean), _p(rstd), acts[b], slope,
-                                      _p(dgb), _p(sums[b]), _p(ws), _stream(x))
-            dgbs.append(dgb)
+        reduced = [_spade_branch_reduce(dh, h, g1, x, mean, rstd, acts[b], slope, sums[b], up)
+                   for b, (dh, h, g1, *_r) in enumerate(branches)]
         work = None
         if need_x and SYNC_BN_GROUP is not None:
             work = _sync_bn_all_reduce(sums, "syncbn_bwd")         # both branches in ONE collective; overlaps with the convs below
         grads = [None] * 11
         for b, (dh, h, g1, actv, wg, wb, base) in enumerate(branches):
-            kh = wg.shape[2]
-            pad = kh // 2
-            if ctx.needs_input_grad[base]:
-                wt = pack_weight(wg, wb, x.dtype, _roundup(actv.shape[3], 128), rows, 1)
-                grads[base] = conv_dgrad(dgbs[b], wt, kh, kh, 1, pad, (hh, ww), actv.shape[3],
-                                         relu_mask=actv if (relus[b] and FUSE_RELU_MASK) else None)
-            need_w = ctx.needs_input_grad[base + 1] or ctx.needs_input_grad[base + 3]
-            need_b = ctx.needs_input_grad[base + 2] or ctx.needs_input_grad[base + 4]
-            sink, slot, db = sinks[b], None, None
-            if sink is not None and need_w and ctx.needs_input_grad[base + 1] and ctx.needs_input_grad[base + 3]:
-                slot = sink[0].grad_slot(wg, wb, sink[2] if need_b else None, sink[3] if need_b else None, kh * kh, rows, actv.shape[3], None)
-            if slot is not None:
-                sink_wgrad(sink[0], slot, actv, dgbs[b], kh, kh, 1, pad, need_b)
-            elif need_w:
-                res = conv_wgrad(actv, dgbs[b], kh, kh, 1, pad, want_bias=need_b)
-                grads[base + 1], grads[base + 3] = unpack_wgrad(res[0] if need_b else res, wg.shape, two=True)
-                db = res[1] if need_b else None
-            elif need_b:
-                db = channel_sums(dgbs[b])[0, 0].float()
-            if db is not None:
-                db = db.reshape(rows // 64, 2, 32)
-                grads[base + 2], grads[base + 4] = db[:, 0].reshape(-1)[:c], db[:, 1].reshape(-1)[:c]
+            grads[base:base + 5] = _spade_branch_grads(ctx.needs_input_grad[base:base + 5], sinks[b], actv, reduced[b][0], wg, wb, relus[b])
         if need_x:
             if work is not None:
                 work.wait()
             d = C.NormApply2Desc()
             for b, (dh, h, g1, *_r) in enumerate(branches):
+                act = reduced[b][1]
                 d.dh[b], d.g1[b], d.sums[b] = dh.data_ptr(), g1.data_ptr(), sums[b].data_ptr()
-                d.h[b] = h.data_ptr() if acts[b] != ACT_NONE else None
-                d.act[b], d.slope[b] = acts[b], slope
+                d.h[b] = h.data_ptr() if act != ACT_NONE else None
+                d.act[b], d.slope[b] = act, slope
             d.x, d.mean, d.rstd = x.data_ptr(), mean.data_ptr(), rstd.data_ptr()
             dx = torch.empty_like(x)
-            d.dx, d.P, d.dtype, d.C = dx.data_ptr(), p, _dt(x), c
+            d.dx, d.P, d.dtype, d.C = dx.data_ptr(), n * hh * ww, _dt(x), c
             d.up, d.H, d.W, d.inv_count = (1 if up else 0), hh, ww, 1.0 / float(count)
-            be.mg_norm_bwd_apply2(d, _stream(x))
+            C.backend().mg_norm_bwd_apply2(d, _stream(x))
             grads[0] = dx
         return tuple(grads) + (None,) * 10
 
@@ -1379,8 +1413,8 @@ class _MaxPoolFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         fuse = ctx.x_relu and FUSE_RELU_MASK
         C.backend().mg_maxpool2_bwd(_p(dy), _p(x), _p(dx), _dt(x), n, h, w, c, 1 if fuse else 0, _stream(x))
-        if fuse:                      # dx already carries the mask of the ReLU that produced x: its conv skips act_backward (see conv_dgrad)
-            _RELU_MASKED[dx.data_ptr()] = (x.data_ptr(), dx._version)
+        if fuse:                      # dx already carries the mask of the ReLU that produced x: its conv skips act_backward
+            _leave_mask_record(dx, x)
         return dx, None
 
 
@@ -1522,14 +1556,14 @@ class _ActTapFn(torch.autograd.Function):
         g1 = g1.contiguous()
         # a gradient that a consumer's data-gradient epilogue / max-pool backward already masked with this ReLU stays correct
         # under a second multiplication by the same 0/1 mask; drop its record, the sum gets a new one
-        _RELU_MASKED.pop(g1.data_ptr(), None)
+        _take_mask_record(g1, a)
         if g2 is not None:
             g2 = g2.contiguous()
-            _RELU_MASKED.pop(g2.data_ptr(), None)
+            _take_mask_record(g2, a)
         out = torch.empty_like(a)
         C.backend().mg_grad_sum_act(_p(g1), _p(g2), _p(a), _p(out), _dt(a), a.numel(), act, slope, _stream(a))
         if act == ACT_RELU:
-            _RELU_MASKED[out.data_ptr()] = (a.data_ptr(), out._version)
+            _leave_mask_record(out, a)
         return out, None, None
 
 
@@ -1657,7 +1691,7 @@ def nearest_pyramid(planes, sizes, cout: int, dtype):
         d.plane[c], d.nstride[c] = _plane_args(pl)
     d.nplanes, d.N, d.H, d.W, d.nlev, d.cout = len(planes), n, H, W, len(sizes), cout
     outs = []
-    d.dtype = C.MG_BF16 if dtype == torch.bfloat16 else C.MG_F32
+    d.dtype = _dtype_code(dtype)
     for l, (h, w) in enumerate(sizes):
         o = torch.empty((n, int(h), int(w), cout), dtype=dtype, device=planes[0].device)
         d.h[l], d.w[l], d.out[l] = int(h), int(w), o.data_ptr()
@@ -1731,7 +1765,7 @@ def bg_compose(image: Optional[torch.Tensor], noise: Optional[torch.Tensor], hai
     hp, hs = _plane_args(hair.detach())
     inp = torch.empty((n, H, W, 8), dtype=dtype, device=src.device)
     back = torch.empty((n, 1, H, W), dtype=torch.float32, device=src.device)
-    C.backend().mg_bg_compose(_p(img), _p(noi), hp, hs, C.MG_BF16 if dtype == torch.bfloat16 else C.MG_F32, n, H, W, int(k), int(mode),
+    C.backend().mg_bg_compose(_p(img), _p(noi), hp, hs, _dtype_code(dtype), n, H, W, int(k), int(mode),
                               _p(inp), _p(back), _stream(src))
     return inp, back
 
@@ -1990,7 +2024,7 @@ class _GaborMaxFn(torch.autograd.Function):
         n, h, w = conf.shape
         g = (dconf.float() * (conf > 0)).contiguous()                 # the clamp at 0 blocks the gradient
         dimg = torch.empty((n, h, w, c), dtype=dtype, device=conf.device)
-        C.backend().mg_gabor_argmax_bwd(_p(g), _p(idx), _p(bank), _p(dimg), C.MG_BF16 if dtype == torch.bfloat16 else C.MG_F32,
+        C.backend().mg_gabor_argmax_bwd(_p(g), _p(idx), _p(bank), _p(dimg), _dtype_code(dtype),
                                         n, h, w, c, _stream(conf))
         return dimg, None
 

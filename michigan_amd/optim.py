@@ -89,8 +89,7 @@ class FlatAdam:
         self._slots: Dict[tuple, _Slot] = {}
         self._slot_list: List[_Slot] = []
         self._gemm_used = 0
-        self._table_host = self._table_dev = self._block_slot_dev = None
-        self._table_event = None
+        self._table = self._block_slot_dev = None                # ops.DeviceTable of C.GradSlot rows; map workgroup -> slot (device)
         self._layout_dirty = True
         self._gbuckets: List[List[int]] = []                     # [lo, hi, nslots] over self.gemm
         self._gpending: List[int] = []
@@ -126,9 +125,9 @@ class FlatAdam:
         self.exp_avg.copy_(m.to(self.exp_avg.device))
         self.exp_avg_sq.copy_(v.to(self.exp_avg.device))
         self.weight_epoch += 1
-        ops._ARENA_PACK_TABLES.pop(id(self), None)              # its job table points into the old parameter storage
+        ops.drop_arena_pack_table(self)                         # its job table points into the old parameter storage
         self.gemm, self._slots, self._slot_list, self._gemm_used, self._layout_dirty = None, {}, [], 0, True
-        self._table_host = self._table_dev = self._block_slot_dev = None
+        self._table = self._block_slot_dev = None
 
     def zero_grad(self, set_to_none: bool = False):
         ops.reset_mask_protocol()                    # no backward pass is in flight here: drop hand-off records an interrupted one left
@@ -235,13 +234,8 @@ class FlatAdam:
     def _freeze_layout(self):
         """(Re)build what depends on the slot set: drain tables and the all-reduce buckets over the GEMM-order arena."""
         dev = self.flat.device
-        block_slot = torch.empty(sum(s.nblocks for s in self._slot_list), dtype=torch.int32)
-        for s in self._slot_list:
-            block_slot[s.first_block:s.first_block + s.nblocks] = s.index
-        self._block_slot_dev = block_slot.to(dev)
-        nbytes = ctypes.sizeof(C.GradSlot) * len(self._slot_list)
-        self._table_host = torch.zeros(nbytes, dtype=torch.uint8, pin_memory=dev.type == "cuda")
-        self._table_dev = self._table_host if dev.type != "cuda" else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._block_slot_dev = ops.block_map([s.nblocks for s in self._slot_list], dev)
+        self._table = ops.DeviceTable(C.GradSlot, len(self._slot_list), dev)
         self._gbuckets, per, lo, n = [], max(self.bucket_bytes // 4, 1), 0, 0
         for s in self._slot_list:
             s.bucket = len(self._gbuckets)
@@ -268,9 +262,7 @@ class FlatAdam:
         ops.wgrad_join(self.gemm.device)                        # weight-gradient launches on the side stream (ops.sink_wgrad)
         if self._layout_dirty:
             self._freeze_layout()
-        if self._table_event is not None:
-            self._table_event.synchronize()                     # last step's upload of the table has long finished
-        tab = (C.GradSlot * len(self._slot_list)).from_address(self._table_host.data_ptr())
+        tab = self._table.begin_update()                        # last step's upload of the table has long finished
         nsn = sum(1 for s in self._slot_list if s.written and s.sn is not None)
         nblk = int(self._block_slot_dev.numel())
         sdot = torch.empty(max(nsn, 1) + (nblk if nsn else 0), dtype=torch.float64, device=self.flat.device)   # s per SN slot, then per-workgroup partials
@@ -291,15 +283,10 @@ class FlatAdam:
                 e.w_sn = e.u = e.v = e.sigma = e.s = None
             e.cout, e.cin, e.taps, e.rows, e.cols, e.swapped = s.cout, s.cin, s.taps, s.rows, s.cols, 0
             e.first_block = s.first_block
-        stream = None
-        if self._table_dev is not self._table_host:
-            self._table_dev.copy_(self._table_host, non_blocking=True)
-            self._table_event = torch.cuda.Event()
-            self._table_event.record()
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.flat.device).cuda_stream)
-        C.backend().mg_grad_drain(ctypes.c_void_p(self._table_dev.data_ptr()), len(self._slot_list),
+        # on a CPU device (the contract emulator) the table is the host buffer itself and the stream is null
+        C.backend().mg_grad_drain(self._table.upload(), len(self._slot_list),
                                   ctypes.c_void_p(self._block_slot_dev.data_ptr()), nblk,
-                                  ctypes.c_void_p(sdot.data_ptr() + 8 * max(nsn, 1)) if nsn else None, stream)
+                                  ctypes.c_void_p(sdot.data_ptr() + 8 * max(nsn, 1)) if nsn else None, ops._stream(self.flat))
         self._reset_step_state()
 
     # ---- overlapped gradient averaging ----------------------------------------------

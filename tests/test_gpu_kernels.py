@@ -786,7 +786,7 @@ def test_side_stream_weight_gradient_survives_inplace_gradient_accumulation():
             x = x0.clone().requires_grad_()
             h = x * 1.0                                           # a non-leaf: its gradient is accumulated in the engine's input buffer
             if side:
-                with torch.cuda.stream(ops._wgrad_side(x.device)[0]):
+                with torch.cuda.stream(ops.side_stream(x.device)):
                     torch.cuda._sleep(40_000_000)                # ~20 ms: every side-stream launch of this backward starts late
             u = h * 2.0
             y = conv(u, resid=h)                                  # the conv's backward hands ONLY dres (== its dy) to h: the first gradient

@@ -45,7 +45,7 @@ def test_trainer_with_weight_gradients_on_the_side_stream_matches_reference_gold
     ops.WGRAD_SIDE_STREAM = True
     try:
         rec, gold = _run("B", "fp32")
-        assert ops._WGRAD_STREAMS and all(not ent[1] for ent in ops._WGRAD_STREAMS.values())     # created, used, and joined at the end
+        assert ops._WGRAD_STREAMS and all(not ent.dirty for ent in ops._WGRAD_STREAMS.values())     # created, used, and joined at the end
     finally:
         ops.WGRAD_SIDE_STREAM = prev
     TP.compare(rec, gold, rtol_loss0=5e-4, rtol_later=RTOL_LATER_HIP, atol_img=1e-3, atol_weight=2 * 4e-4 * 2 + 1e-5)

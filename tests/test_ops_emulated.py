@@ -159,6 +159,74 @@ def test_packed_weight_cache_follows_flat_adam_updates(emulator_backend):
         del w2
 
 
+def test_derived_tensors_of_parameters_are_cached_until_the_parameter_changes(emulator_backend):
+    """The one cache rule behind ops.pack_weight and ops.spade_bias_rows, through the public functions: an unchanged nn.Parameter is
+    served the same tensor object; an in-place torch write (version counter) or a FlatAdam step (arena update count) makes the next
+    call return the new values; tensors that are not parameters are never cached."""
+    from michigan_amd import ops
+    from michigan_amd.optim import FlatAdam
+    torch.manual_seed(1)
+    pack = lambda w, w1=None: ops.pack_weight(w, w1, torch.float32, 128, 8, 0)
+    image = lambda w: ops._pack_weight(w, None, torch.float32, 128, 8, 0)           # the uncached per-layer pack
+    rows = lambda a, b: ops._interleave32(a.detach().float(), b.detach().float())
+    w = torch.nn.Parameter(torch.randn(8, 8, 3, 3))
+    bg, bb = torch.nn.Parameter(torch.randn(40)), torch.nn.Parameter(torch.randn(40))
+    # unchanged parameter: the same object
+    p0, r0 = pack(w), ops.spade_bias_rows(bg, bb)
+    assert pack(w) is p0 and ops.spade_bias_rows(bg, bb) is r0
+    assert torch.equal(p0, image(w)) and torch.equal(r0, rows(bg, bb))
+    # in-place write under no_grad: a new tensor with the new values
+    with torch.no_grad():
+        w.mul_(2)
+        bb.add_(1)
+    p1, r1 = pack(w), ops.spade_bias_rows(bg, bb)
+    assert p1 is not p0 and r1 is not r0
+    assert torch.equal(p1, image(w)) and torch.equal(r1, rows(bg, bb)) and not torch.equal(p1, p0) and not torch.equal(r1, r0)
+    assert pack(w) is p1 and ops.spade_bias_rows(bg, bb) is r1
+    # not a parameter: never cached
+    t, ta, tb = w.detach().clone(), bg.detach().clone(), bb.detach().clone()
+    assert pack(t) is not pack(t) and ops.spade_bias_rows(ta, tb) is not ops.spade_bias_rows(ta, tb)
+    assert ops.spade_bias_rows(bg, tb) is not ops.spade_bias_rows(bg, tb)
+    # parameters of a FlatAdam arena: the optimiser's update count invalidates, the batched re-pack refreshes IN PLACE
+    wg, wb = torch.nn.Parameter(torch.randn(8, 8, 3, 3)), torch.nn.Parameter(torch.randn(8, 8, 3, 3))
+    opt = FlatAdam([w, wg, wb, bg, bb], lr=0.1)
+    p2, q2, r2 = pack(w), pack(wg, wb), ops.spade_bias_rows(bg, bb)
+    assert pack(w) is p2 and pack(wg, wb) is q2 and ops.spade_bias_rows(bg, bb) is r2
+    addr, old, old_rows = p2.data_ptr(), p2.clone(), r2.clone()
+    with torch.no_grad():
+        opt.flat.mul_(3)                        # what the Adam kernel does: the arena changes, no parameter's version counter moves
+    opt.weight_epoch += 1
+    p3 = pack(w)
+    assert p3.data_ptr() == addr and torch.equal(p3, image(w)) and torch.equal(p3, old * 3)
+    assert pack(w) is p3                                                            # ... and the call after that is a hit
+    q3 = pack(wg, wb)                                                               # refreshed by the same batched launch
+    assert q3 is q2 and torch.equal(q3, ops._pack_weight(wg, wb, torch.float32, 128, 8, 0))
+    r3 = ops.spade_bias_rows(bg, bb)
+    assert torch.equal(r3, rows(bg, bb)) and torch.equal(r3, old_rows * 3) and ops.spade_bias_rows(bg, bb) is r3
+
+
+def test_param_cache_does_not_serve_another_object_at_the_same_key(emulator_backend):
+    """A freed parameter's address (and version 0) can be taken by a new parameter: the entry stored for the first object is not
+    served to a second one that presents the same key, is not counted as "stale only by the arena's update count", and goes when
+    dead entries are dropped."""
+    from michigan_amd import ops
+    cache = ops._ParamCache()
+    a, b = torch.nn.Parameter(torch.zeros(4)), torch.nn.Parameter(torch.zeros(4))
+    value = torch.ones(1)
+    cache.put("key", (a,), value)
+    assert cache.get("key", (a,)) is value
+    assert cache.get("key", (b,)) is None and not cache.only_epoch_moved("key", (b,))
+    assert cache.get("other", (a,)) is None
+    with torch.no_grad():
+        a.add_(1)
+    assert cache.get("key", (a,)) is None and not cache.only_epoch_moved("key", (a,))     # the version moved
+    cache.restamp("key")
+    assert cache.get("key", (a,)) is value
+    del a
+    cache.prune()
+    assert not list(cache.live(None)) and cache.get("key", (b,)) is None
+
+
 def test_hinge_and_wide_edge_match_reference_formula(emulator_backend):
     """f1: the fused hinge / wide-edge ops (on the contract emulator here, on the HIP kernels in tests/test_gpu_kernels.py)
     against the reference formula written with plain torch ops (loss.py:60-111), values and gradients."""

@@ -24,4 +24,4 @@ for rep in range(4):
         torch.cuda.synchronize()
         print(f"weight gradients on the side stream = {v}: {(time.perf_counter() - t0) / 6 * 1e3:.2f} ms/step", flush=True)
 ent = list(ops._WGRAD_STREAMS.values())
-print("side stream:", ent[0][0] if ent else None, "priority", getattr(ent[0][0], "priority", "?") if ent else "")
+print("side stream:", ent[0].stream if ent else None, "priority", getattr(ent[0].stream, "priority", "?") if ent else "")
