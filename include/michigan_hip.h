@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MG_ABI_VERSION 8
+#define MG_ABI_VERSION 9
 
 enum { MG_F32 = 0, MG_BF16 = 1 };
 enum { MG_ACT_NONE = 0, MG_ACT_RELU = 1, MG_ACT_LRELU = 2, MG_ACT_TANH = 3 };
@@ -496,6 +496,34 @@ int mg_color_loss_fwd(const void* img, const float* real, int64_t real_nstride, 
 int mg_color_loss_bwd(const void* img, const float* real, int64_t real_nstride, const float* back, int64_t back_nstride,
                       const float* g_lab, const float* g_rgb, const float* g_back,
                       int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flags, void* dimg, void* stream);
+
+/* The two image-space terms of the unpaired training stage (curr_step = 2) in one pass over the generated image (mg_hair_lab.hip):
+ * HairAvgLabLoss.forward (loss.py:534-621, called at pix2pix_model.py:356-358; balance_Lab off) and RGBBackgroundL1Loss.forward
+ * (loss.py:388-400, called at pix2pix_model.py:362-363).
+ * img: the generated image as in mg_color_loss_fwd (NHWC [N,H,W,C] in `dtype`, RGB in channels 0..2).  ref (= image_ref) and tgt
+ * (= image_tag): fp32, three dense planes [H,W] per sample at a sample stride.  hair_tag (m_f), hair_ref (m_r), back (m_b): fp32 planes
+ * [H,W] at a sample stride (channel 1 of the tag label, channel 1 of the reference label, channel 0 of the tag label -- channel views of
+ * an NCHW one-hot label are passed without a copy).  a(x), b(x) as in mg_color_loss_fwd.  Per sample n:
+ *   S_f = sum_p m_f, S_r = sum_p m_r (a sum that is 0 is replaced by 1), A_f = sum_p m_f a(img), B_f = sum_p m_f b(img),
+ *   A_r = sum_p m_r a(ref), B_r = sum_p m_r b(ref) (the mask VALUE multiplies), da = A_f / S_f - A_r / S_r, db = B_f / S_f - B_r / S_r.
+ * `flags` selects the terms (a term not selected costs nothing, reads nothing, and its operands may be NULL):
+ *   bit 0  out[0] = hairAvgLab = (1 / 2N) sum_n (|da[n]| + |db[n]|)
+ *   bit 1  out[1] = background = mean |img m_b - tgt m_b| over N*3*H*W (bit 2 of mg_color_loss_fwd, same definition)
+ * out: 2 floats, 0 for a term not selected.  stats: 4 N floats, 16-byte aligned, written when bit 0 is set: {da, db, 1 / S_f, 1 / S_r}
+ * of sample n at stats + 4 n -- the backward reads it and reduces nothing.  ws: >= 7 * max(1024, N) floats (one partial per workgroup
+ * and sum; a workgroup belongs to one sample; summed in a fixed order in double, so loss and gradient are bit-reproducible and do not
+ * depend on which other bit is set).  Pixels whose mask is 0 are not read: img where m_f == 0 (bit 0) and m_b == 0 (bit 1), ref where
+ * m_r == 0, tgt where m_b == 0.  All per-pixel arithmetic fp32.  Two launches.
+ * bwd (one launch): dimg = d(g_hair[0] out[0] + g_back[0] out[1]) / d img in the image's dtype and layout, channels 3..C-1 zero;
+ *   d out[0] / d img[n,p,c] = m_f[n,p] / (2N S_f[n]) (sign(da[n]) da/dx_c + sign(db[n]) db/dx_c) at pixel p, sign(0) = 0;
+ * the g_* are device scalars, a NULL pointer = 0.  ref, tgt and the masks get no gradient.  N <= 65535. */
+int mg_hair_lab_fwd(const void* img, const float* ref, int64_t ref_nstride, const float* hair_tag, int64_t hair_tag_nstride,
+                    const float* hair_ref, int64_t hair_ref_nstride, const float* tgt, int64_t tgt_nstride,
+                    const float* back, int64_t back_nstride, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C,
+                    int32_t flags, float* out, float* stats, float* ws, void* stream);
+int mg_hair_lab_bwd(const void* img, const float* hair_tag, int64_t hair_tag_nstride, const float* tgt, int64_t tgt_nstride,
+                    const float* back, int64_t back_nstride, const float* stats, const float* g_hair, const float* g_back,
+                    int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flags, void* dimg, void* stream);
 
 /* ---------------------------------------------------------------------------
  * (iv) Collectives over RCCL / xGMI -- SURVEY.md section 8b's last export group.  One communicator per process (= per GPU); what the

@@ -12,9 +12,10 @@ What the reference's plug-in mechanism needs (models/networks/__init__.py:16-48,
   * the trainer imports `DataParallelWithCallback` from `models.networks.sync_batchnorm` (trainers/pix2pix_trainer.py:6).
 install() therefore patches exactly those names, in the reference's own modules, with subclasses of the HIP classes
 that ALSO inherit the reference's `BaseNetwork` (so the `issubclass` assertion holds), and leaves every other name of
-the reference package (StyleContentLoss, HairAvgLabLoss, ConvEncoder, the other generators, ...) in place.  `LabColorLoss`
-and `RGBBackgroundL1Loss` are patched too: the reference's `LabColorLoss` raises on torch >= 1.2 (`1 - mask` on a bool
-mask, loss.py:443,472), so the published training command -- which keeps the Lab term on -- needs the patched one to run.
+the reference package (StyleContentLoss, ConvEncoder, the other generators, ...) in place.  `LabColorLoss`, `HairAvgLabLoss`
+and `RGBBackgroundL1Loss` are patched too: the reference's two Lab classes raise on torch >= 1.2 (`1 - mask` on a bool
+mask, loss.py:443,472,546,565), so the published training command -- which keeps the Lab term on -- and `--unpairTrain`
+need the patched ones to run.
 `criterionRGBL1` is a plain `nn.L1Loss` the reference builds itself (pix2pix_model.py:51) and stays ATen.
 
 Only the three top-level networks (+ the frozen in-painting net) and the loss classes are swapped: they take and
@@ -241,8 +242,9 @@ def install(compute_dtype: Optional[str] = "fp32", losses: bool = True, data_par
         # (subclasses that live, by name, in the reference's module like VGGLoss above)
         LabColorLoss = type("LabColorLoss", (hip.LabColorLoss,), {"__module__": "models.networks.loss", "_mg_dropin": True})
         RGBBackgroundL1Loss = type("RGBBackgroundL1Loss", (hip.RGBBackgroundL1Loss,), {"__module__": "models.networks.loss", "_mg_dropin": True})
+        HairAvgLabLoss = type("HairAvgLabLoss", (hip.HairAvgLabLoss,), {"__module__": "models.networks.loss", "_mg_dropin": True})
         for name, cls in (("GANLoss", hip.GANLoss), ("GANFeatLoss", hip.GANFeatLoss), ("VGGLoss", VGGLoss), ("L1OLoss", hip.L1OLoss),
-                          ("LabColorLoss", LabColorLoss), ("RGBBackgroundL1Loss", RGBBackgroundL1Loss)):
+                          ("LabColorLoss", LabColorLoss), ("RGBBackgroundL1Loss", RGBBackgroundL1Loss), ("HairAvgLabLoss", HairAvgLabLoss)):
             _set("models.networks.loss", name, cls)
             _set("models.networks", name, cls)
             patched[name] = cls

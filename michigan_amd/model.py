@@ -7,8 +7,11 @@ sit on the hot path under the README flags:  hinge GAN (wide_edge), discriminato
 matching, VGG perceptual loss and the Gabor orientation loss (on by default in the reference), and the image-space
 Lab colour / RGB / background L1 terms (pix2pix_model.py:317-336) as one fused pass.  The published training recipe keeps
 the Lab term ON (`no_lab_loss=False`); `default_options()` leaves the three terms off because the committed fixtures and
-the benchmark's history were recorded without them.  Style / content, HairAvgLab, balance_Lab and the blender are outside
-this tier's scope.
+the benchmark's history were recorded without them.  With `unpairTrain` the second training stage exists too
+(train.py:41-90 runs every epoch at `curr_step = 2` on unpaired data, then at 1 on paired data): at step 2 the discriminator
+is a second network `netD2` with its own Adam (pix2pix_model.py:147-150,568-572, pix2pix_trainer.py:61-77) and the generator
+objective is GAN + ORIENT (+ CONFIDENCE) + hairAvgLab + background (pix2pix_model.py:352-363), the last two as one fused
+pass (mg_hair_lab_*).  Style / content, balance_Lab and the blender are outside this tier's scope.
 
 Differences that do not change results (SURVEY.md section 8a "parity-preserving minimum"):
   * the discriminator's parameters do not require grad during the generator step (their
@@ -67,6 +70,8 @@ def default_options(**over) -> argparse.Namespace:
         # here so that the recorded fixtures and benchmark numbers keep their objective -- switch them on per run
         no_lab_loss=True, no_rgb_loss=True, no_background_loss=True, lambda_lab=1.0, lambda_rgb=1.0, lambda_background=1.0,
         balance_Lab=False,
+        # the unpaired training stage (train_options.py:38-41): netD2 + hairAvgLab at curr_step == 2
+        unpairTrain=False, lambda_hairavglab=1.0, same_netD_model=False,
     )
     d.update(over)
     return argparse.Namespace(**d)
@@ -78,6 +83,7 @@ class Pix2PixModel(nn.Module):
         self.opt = opt
         self.netG = networks.define_G(opt)
         self.netD = networks.define_D(opt) if opt.isTrain else None
+        self.netD2 = networks.define_D(opt) if opt.isTrain and getattr(opt, "unpairTrain", False) else None
         if opt.isTrain:
             self.criterionGAN = networks.GANLoss(opt.gan_mode, opt=opt)
             self.criterionGANFeat = networks.GANFeatLoss(opt)
@@ -90,6 +96,8 @@ class Pix2PixModel(nn.Module):
                 self.criterionOrient = networks.L1OLoss(opt)
             if not getattr(opt, "no_lab_loss", True) and getattr(opt, "balance_Lab", False):
                 raise NotImplementedError("Lab colour loss: the balance_Lab weighting is not implemented")
+            if getattr(opt, "unpairTrain", False):
+                self.criterionHairAvgLab = networks.HairAvgLabLoss(opt)
         self.netIG = None
         if getattr(opt, "inpaint_orient", False):
             self.netIG = networks.define_IG(opt).eval()          # frozen (pix2pix_model.py:196-198)
@@ -184,6 +192,13 @@ class Pix2PixModel(nn.Module):
         return self.netG(d["input_ref"], orient_mask=d["orient"], image_ref=d["image_ref"],
                          input_tag=d["input_tag"], noise=d["noise"], image_tag=d["image_tag"])
 
+    def _unpaired_step(self):
+        return bool(getattr(self.opt, "unpairTrain", False)) and self.opt.curr_step == 2
+
+    def _discriminator_in_use(self):
+        """netD2 scores the unpaired stage, netD the paired one (pix2pix_model.py:568-572)."""
+        return self.netD2 if self._unpaired_step() else self.netD
+
     def discriminate(self, d, fake_image, split=False):
         """D([tag one-hot | orientation | image]) on fake and real stacked along the batch
         (pix2pix_model.py:546-594).  The 7-channel input is assembled directly in the kernels' NHWC layout
@@ -196,27 +211,28 @@ class Pix2PixModel(nn.Module):
         pass just updated (sigma = u.W v either way) and there is no dropout / running statistic in D (InstanceNorm), so the
         outputs are the stacked pass's outputs."""
         from . import ops
+        netD = self._discriminator_in_use()
         dt = fake_image.dtype
         n, _, h, w = fake_image.shape
         cond = torch.cat([d["input_tag"], self.orientation_planes(d)], dim=1)                 # [N,4,H,W] fp32
         if split and SPLIT_D_IN_G_STEP:
             fin = torch.empty((n, h, w, 8), dtype=dt, device=fake_image.device)
             fin = ops.assemble_nhwc8(fin, 0, cond, fake_image.permute(0, 2, 3, 1), cf=3)
-            pred_fake = self.netD(fin.permute(0, 3, 1, 2))
+            pred_fake = netD(fin.permute(0, 3, 1, 2))
             rin = torch.empty((n, h, w, 8), dtype=dt, device=fake_image.device)
             ops.assemble_nhwc8(rin, 0, torch.cat([cond, d["image_tag"]], dim=1))
-            was_training = self.netD.training
-            self.netD.eval()
+            was_training = netD.training
+            netD.eval()
             try:
                 with torch.no_grad():
-                    pred_real = self.netD(rin.permute(0, 3, 1, 2))
+                    pred_real = netD(rin.permute(0, 3, 1, 2))
             finally:
-                self.netD.train(was_training)
+                netD.train(was_training)
             return pred_fake, pred_real
         both = torch.empty((2 * n, h, w, 8), dtype=dt, device=fake_image.device)
         ops.assemble_nhwc8(both, n, torch.cat([cond, d["image_tag"]], dim=1))                  # real half: all planar, no gradient
         both = ops.assemble_nhwc8(both, 0, cond, fake_image.permute(0, 2, 3, 1), cf=3)         # fake half: the generator's NHWC image
-        out = self.netD(both.permute(0, 3, 1, 2))
+        out = netD(both.permute(0, 3, 1, 2))
         half = lambda t: t.size(0) // 2
         pred_fake = [[t[:half(t)] for t in p] for p in out]
         pred_real = [[t[half(t):] for t in p] for p in out]
@@ -319,6 +335,12 @@ class Pix2PixModel(nn.Module):
                     losses["rgb"] = _scaled(rgb, getattr(self.opt, "lambda_rgb", 1.0))
                 if flags & ops.COLOR_LAB:
                     losses["lab"] = _scaled(lab, getattr(self.opt, "lambda_lab", 1.0))
+        if self._unpaired_step():
+            # hairAvgLab + background (pix2pix_model.py:352-363; background regardless of no_background_loss there): ONE pass over fake
+            hair, back = ops.hair_lab_losses(fake.permute(0, 2, 3, 1), d["image_ref"], d["input_tag"].detach()[:, 1], d["input_ref"].detach()[:, 1],
+                                             d["image_tag"], d["input_tag"].detach()[:, 0], ops.HAIR_LAB | ops.HAIR_BACKGROUND)
+            losses["hairAvgLab"] = _scaled(hair, getattr(self.opt, "lambda_hairavglab", 1.0))
+            losses["background"] = _scaled(back, getattr(self.opt, "lambda_background", 1.0))
         if branch:
             main.wait_stream(side)                                # the D branch's loss scalars are summed on the main stream
             for k in ("GAN", "GAN_Feat") + (("ORIENT", "CONFIDENCE") if int(ops.BRANCH_STREAMS) >= 3 else ()):
@@ -353,10 +375,11 @@ class Pix2PixModel(nn.Module):
         return os.path.join(self.opt.checkpoints_dir, self.opt.name, "%s_net_%s.pth" % (epoch, label))
 
     def save(self, epoch):
-        """`<epoch>_net_G.pth` / `<epoch>_net_D.pth`: plain state_dicts with the reference's keys, loadable by the reference.
+        """`<epoch>_net_G.pth` / `<epoch>_net_D.pth` (/ `<epoch>_net_D2.pth` with unpairTrain, pix2pix_model.py:161-162): plain state_dicts
+        with the reference's keys, loadable by the reference.
         Data parallel: call on EVERY rank; rank 0 writes (temporary file + rename, so a reader never sees a torn file) and the outcome
         is broadcast -- a failed write raises on all ranks and leaves no temporary file (parallel.rank0_write)."""
-        for label, net in (("G", self.netG), ("D", self.netD)):
+        for label, net in (("G", self.netG), ("D", self.netD), ("D2", self.netD2)):
             if net is not None:
                 sd = {k: v.detach().cpu() for k, v in net.state_dict().items()} if parallel.rank() == 0 else None
                 parallel.rank0_write(self._ckpt_path(label, epoch), lambda tmp, sd=sd: torch.save(sd, tmp),
@@ -364,12 +387,15 @@ class Pix2PixModel(nn.Module):
 
     def load(self, epoch):
         """util.load_network semantics: copy by key, skip unknown keys, strip a leading 'module.' (multi-GPU files).  The
-        parameters are updated in place, so flat optimiser arenas stay attached."""
+        parameters are updated in place, so flat optimiser arenas stay attached.  netD2 comes from `<epoch>_net_D2.pth`, or from
+        `<epoch>_net_D.pth` with `same_netD_model` or when there is no D2 file (a checkpoint of a paired-only run)."""
         import os
-        for label, net in (("G", self.netG), ("D", self.netD)):
+        for label, net in (("G", self.netG), ("D", self.netD), ("D2", self.netD2)):
             path = self._ckpt_path(label, epoch)
             if net is None:
                 continue
+            if label == "D2" and (getattr(self.opt, "same_netD_model", False) or not os.path.exists(path)):
+                path = self._ckpt_path("D", epoch)
             if not os.path.exists(path):                       # util.load_network raises too (torch.load on a missing file)
                 raise FileNotFoundError("checkpoint %s does not exist" % path)
             own = net.state_dict()
@@ -385,8 +411,11 @@ class Pix2PixModel(nn.Module):
             betas, g_lr, d_lr = (opt.beta1, opt.beta2), opt.lr, opt.lr
         else:
             betas, g_lr, d_lr = (0.0, 0.9), opt.lr / 2, opt.lr * 2
-        return (FlatAdam(self.netG.parameters(), lr=g_lr, betas=betas, group=group),
-                FlatAdam(self.netD.parameters(), lr=d_lr, betas=betas, group=group))
+        optimizers = (FlatAdam(self.netG.parameters(), lr=g_lr, betas=betas, group=group),
+                      FlatAdam(self.netD.parameters(), lr=d_lr, betas=betas, group=group))
+        if self.netD2 is not None:                           # pix2pix_model.py:147-150: D's lr and betas
+            optimizers += (FlatAdam(self.netD2.parameters(), lr=d_lr, betas=betas, group=group),)
+        return optimizers
 
 
 class Pix2PixTrainer:
@@ -402,14 +431,24 @@ class Pix2PixTrainer:
         if group is not None:
             parallel.broadcast_parameters(self.pix2pix_model.netG)
             parallel.broadcast_parameters(self.pix2pix_model.netD)
+            if self.pix2pix_model.netD2 is not None:
+                parallel.broadcast_parameters(self.pix2pix_model.netD2)
             if self.pix2pix_model.netIG is not None:
                 parallel.broadcast_parameters(self.pix2pix_model.netIG)
-        self.optimizer_G, self.optimizer_D = self.pix2pix_model.create_optimizers(opt, group)
+        self.optimizer_D2 = None
+        if getattr(opt, "unpairTrain", False):               # pix2pix_trainer.py:30-33
+            self.optimizer_G, self.optimizer_D, self.optimizer_D2 = self.pix2pix_model.create_optimizers(opt, group)
+        else:
+            self.optimizer_G, self.optimizer_D = self.pix2pix_model.create_optimizers(opt, group)
         self.old_lr = opt.lr
         self.g_losses, self.d_losses, self.generated = {}, {}, None
 
+    def _optimizer_d_in_use(self):
+        """optimizer_D2 during the unpaired stage (pix2pix_trainer.py:61-77)."""
+        return self.optimizer_D2 if self.optimizer_D2 is not None and self.opt.curr_step == 2 else self.optimizer_D
+
     def _set_d_requires_grad(self, flag: bool):
-        for p in self.optimizer_D.params:
+        for p in self._optimizer_d_in_use().params:
             p.requires_grad_(flag)
 
     def run_generator_one_step(self, data):
@@ -429,12 +468,17 @@ class Pix2PixTrainer:
         self.g_losses, self.generated = g_losses, generated
 
     def run_discriminator_one_step(self, data):
-        self.optimizer_D.zero_grad()
+        optimizer = self._optimizer_d_in_use()
+        optimizer.zero_grad()
         d_losses = self.pix2pix_model(data, mode="discriminator")
         d_loss = _total(d_losses)
         d_loss.backward()
-        self.optimizer_D.step()
+        optimizer.step()
         self.d_losses = d_losses
+
+    def init_losses(self):
+        """pix2pix_trainer.py:91-93: train.py calls it between the two stages of an epoch."""
+        self.g_losses, self.d_losses = {}, {}
 
     def get_latest_losses(self):
         return {**self.g_losses, **self.d_losses}
@@ -444,20 +488,26 @@ class Pix2PixTrainer:
         torch.optim.Adam's state_dict layout, `<epoch>_optim.pth`), so that training resumes exactly."""
         import os
         self.pix2pix_model_on_one_gpu.save(epoch)
-        sd = {"G": self.optimizer_G.state_dict(), "D": self.optimizer_D.state_dict(), "old_lr": self.old_lr} if parallel.rank() == 0 else None
+        sd = None
+        if parallel.rank() == 0:
+            sd = {"G": self.optimizer_G.state_dict(), "D": self.optimizer_D.state_dict(), "old_lr": self.old_lr}
+            if self.optimizer_D2 is not None:
+                sd["D2"] = self.optimizer_D2.state_dict()
         parallel.rank0_write(os.path.join(self.opt.checkpoints_dir, self.opt.name, "%s_optim.pth" % epoch), lambda tmp: torch.save(sd, tmp),
                              device=self.optimizer_G.flat.device)
 
     def load(self, epoch):
         import os
         self.pix2pix_model_on_one_gpu.load(epoch)
-        for o in (self.optimizer_G, self.optimizer_D):
+        for o in (self.optimizer_G, self.optimizer_D) + ((self.optimizer_D2,) if self.optimizer_D2 is not None else ()):
             o.weight_epoch += 1                      # parameters were rewritten in place: packed weight images are stale
         path = os.path.join(self.opt.checkpoints_dir, self.opt.name, "%s_optim.pth" % epoch)
         if os.path.exists(path):
             sd = torch.load(path, map_location="cpu")
             self.optimizer_G.load_state_dict(sd["G"])
             self.optimizer_D.load_state_dict(sd["D"])
+            if self.optimizer_D2 is not None and "D2" in sd:
+                self.optimizer_D2.load_state_dict(sd["D2"])
             self.old_lr = sd.get("old_lr", self.old_lr)
 
     def get_latest_generated(self):
@@ -471,4 +521,5 @@ class Pix2PixTrainer:
                 grp["lr"] = g
             for grp in self.optimizer_D.param_groups:
                 grp["lr"] = d
+            # optimizer_D2 keeps its initial lr: the reference never touches it (pix2pix_trainer.py:99-119) -- parity first, see INTEGRATION.md
             self.old_lr = new_lr

@@ -3,8 +3,9 @@
 Reductions run in fp32 on whatever dtype the discriminator / VGG towers produced, as fused HIP launches: the hinge GAN
 loss with its wide-edge weight mask (mg_hinge_*, mg_wide_edge_weight), discriminator feature matching and the VGG taps
 (mg_l1_mean_*), the Gabor orientation loss (mg_gabor_argmax_*), and the image-space Lab colour / background / RGB L1
-terms as one pass (mg_color_loss_*).  Style / content, HairAvgLab and the balance_Lab weighting are out of scope
- and stay the reference's own classes under michigan_amd.dropin."""
+terms as one pass (mg_color_loss_*), and the unpaired stage's hair-average Lab term (mg_hair_lab_*, fused with the background
+term in the model).  Style / content and the balance_Lab weighting are out of scope; style / content
+stay the reference's own classes under michigan_amd.dropin."""
 from __future__ import annotations
 
 import math
@@ -240,3 +241,18 @@ class LabColorLoss(nn.Module):
 
     def forward(self, fake, real, mask=None):
         return ops.color_losses(_image_nhwc(fake), real, None, ops.COLOR_LAB)[0]
+
+
+class HairAvgLabLoss(nn.Module):
+    """L1 between the mean Lab (a, b) colour of the generated hair inside `mask_fake` and of the reference image's hair inside
+    `mask_real`, one pair of means per sample (reference: loss.py:534-621; masks [N, 1, H, W], their values multiply; an empty
+    mask divides by 1).  `opt.balance_Lab` (needs `opt.weight_dir` and a grid_sample whose default changed) is not implemented."""
+
+    def __init__(self, opt):
+        super().__init__()
+        if getattr(opt, "balance_Lab", False):
+            raise NotImplementedError("hair-average Lab loss: the balance_Lab weighting is not implemented")
+        self.opt = opt
+
+    def forward(self, fake, real, mask_fake, mask_real):
+        return ops.hair_lab_losses(_image_nhwc(fake), real, mask_fake.detach()[:, 0], mask_real.detach()[:, 0], flags=ops.HAIR_LAB)[0]

@@ -1907,6 +1907,90 @@ def color_losses(fake: torch.Tensor, real: torch.Tensor, back: Optional[torch.Te
     return _ColorLossFn.apply(fake, real, back, flags)
 
 
+HAIR_LAB, HAIR_BACKGROUND = 1, 2                      # `flags` bits of mg_hair_lab_*
+
+
+class _HairLabLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, ref, hair_tag, hair_ref, tgt, back, flags):
+        img = _nhwc(img)
+        n, h, w, c = img.shape
+        out = torch.empty(2, dtype=torch.float32, device=img.device)
+        stats = torch.empty(4 * n, dtype=torch.float32, device=img.device) if flags & HAIR_LAB else None
+        ws = torch.empty(7 * max(1024, n), dtype=torch.float32, device=img.device)
+        plane = lambda t: _plane_args(t) if t is not None else (None, 0)
+        (fp, fs), (rp, rs), (bp, bs) = plane(hair_tag), plane(hair_ref), plane(back)
+        C.backend().mg_hair_lab_fwd(_p(img), _p(ref), ref.stride(0) if ref is not None else 0, fp, fs, rp, rs,
+                                    _p(tgt), tgt.stride(0) if tgt is not None else 0, bp, bs, _dt(img), n, h, w, c, flags,
+                                    _p(out), _p(stats), _p(ws), _stream(img))
+        ctx.save_for_backward(img, hair_tag, tgt, back, stats)
+        ctx.flags = flags
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_hair, g_back):
+        img, hair_tag, tgt, back, stats = ctx.saved_tensors
+        if g_hair is None and g_back is None:
+            return (None,) * 7
+        n, h, w, c = img.shape
+        fix = lambda g: None if g is None else (g if g.dtype == torch.float32 else g.float())
+        g_hair, g_back = fix(g_hair), fix(g_back)
+        plane = lambda t: _plane_args(t) if t is not None else (None, 0)
+        (fp, fs), (bp, bs) = plane(hair_tag), plane(back)
+        d = torch.empty_like(img)
+        C.backend().mg_hair_lab_bwd(_p(img), fp, fs, _p(tgt), tgt.stride(0) if tgt is not None else 0, bp, bs, _p(stats),
+                                    _p(g_hair), _p(g_back), _dt(img), n, h, w, c, ctx.flags, _p(d), _stream(img))
+        return (d,) + (None,) * 6
+
+
+def hair_lab_losses(fake: torch.Tensor, image_ref: Optional[torch.Tensor], hair_tag: Optional[torch.Tensor],
+                    hair_ref: Optional[torch.Tensor], image_tag: Optional[torch.Tensor] = None, back: Optional[torch.Tensor] = None,
+                    flags: int = HAIR_LAB):
+    """(hairAvgLab, background) of the unpaired stage's generator objective (HairAvgLabLoss loss.py:534-621 without balance_Lab,
+    RGBBackgroundL1Loss loss.py:388-400; pix2pix_model.py:352-363) in one pass: fake NHWC [N, H, W, C >= 3] bf16 / fp32 with RGB in
+    channels 0..2, image_ref / image_tag NCHW [N, 3, H, W], hair_tag / hair_ref / back fp32 [N, H, W] views (channel 1 of the tag label,
+    channel 1 of the reference label, channel 0 of the tag label).  `flags`: HAIR_LAB | HAIR_BACKGROUND; a term not selected is 0, costs
+    nothing and its operands may be None.  Two fp32 scalars (views of one tensor), gradient to `fake` only.  Two launches forward, one
+    backward."""
+    flags = int(flags)
+    if not 1 <= flags <= 3:
+        raise ValueError("hair_lab_losses: flags must select at least one of HAIR_LAB, HAIR_BACKGROUND")
+    if fake.dim() != 4 or fake.shape[-1] < 3:
+        raise ValueError(f"hair_lab_losses: expected an NHWC image with at least 3 channels, got {tuple(fake.shape)}")
+    n, h, w = fake.shape[0], fake.shape[1], fake.shape[2]
+
+    def image(t, name):
+        if t is None:
+            raise ValueError("hair_lab_losses: %s is needed for the selected terms" % name)
+        if t.dim() != 4 or tuple(t.shape) != (n, 3, h, w):
+            raise ValueError(f"hair_lab_losses: NHWC image {tuple(fake.shape)} does not match the NCHW {name} {tuple(t.shape)}")
+        t = t.detach()
+        if t.dtype != torch.float32:
+            t = t.float()
+        return t if t.is_contiguous() else t.contiguous()
+
+    def plane(t, name):
+        if t is None:
+            raise ValueError("hair_lab_losses: %s is needed for the selected terms" % name)
+        t = t.detach()
+        if t.dtype != torch.float32:
+            t = t.float()
+        if tuple(t.shape) != (n, h, w):
+            raise ValueError(f"hair_lab_losses: {name} {tuple(t.shape)} does not match the image")
+        return t if (t.stride(2) == 1 and t.stride(1) == t.shape[2]) else t.contiguous()
+
+    if flags & HAIR_LAB:
+        image_ref, hair_tag, hair_ref = image(image_ref, "image_ref"), plane(hair_tag, "the tag hair plane"), plane(hair_ref, "the reference hair plane")
+    else:
+        image_ref = hair_tag = hair_ref = None
+    if flags & HAIR_BACKGROUND:
+        image_tag, back = image(image_tag, "image_tag"), plane(back, "the background plane")
+    else:
+        image_tag = back = None
+    return _HairLabLossFn.apply(fake, image_ref, hair_tag, hair_ref, image_tag, back, flags)
+
+
 class _WeightedSumFn(torch.autograd.Function):
     """sum_k w_k * v_k of K scalar tensors as THREE launches forward (stack, mul, sum) and ONE backward (g * w), whatever K: the loss
     modules used to chain `total = total + val * w` -- 2 launches forward and 2 backward per term, ~100 five-microsecond

@@ -14,18 +14,23 @@ from typing import Dict
 import torch
 
 
-def synth_batch(n: int, size: int, seed: int = 1234) -> Dict[str, torch.Tensor]:
-    """The tensors Pix2PixModel.preprocess_input hands to the networks (pix2pix_model.py:209-254),
-    NCHW float32 on CPU: one-hot tag/ref label maps [n,2,s,s], 2-channel orientation (use_ig form),
-    images and noise [n,3,s,s]."""
-    g = torch.Generator().manual_seed(seed)
+def _ellipses(n: int, size: int, g: torch.Generator) -> torch.Tensor:
     yy, xx = torch.meshgrid(torch.arange(size, dtype=torch.float32), torch.arange(size, dtype=torch.float32), indexing="ij")
     masks = []
     for _ in range(n):
         cy, cx = (size / 2 + (torch.rand(2, generator=g) * 2 - 1) * size / 16).tolist()
         ry, rx = (size * (100 + torch.rand(2, generator=g) * 80) / 512).tolist()
         masks.append((((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 <= 1.0).float())
-    hair = torch.stack(masks)[:, None]                                     # [n,1,s,s] in {0,1}
+    return torch.stack(masks)[:, None]                                     # [n,1,s,s] in {0,1}
+
+
+def synth_batch(n: int, size: int, seed: int = 1234, unpaired: bool = False) -> Dict[str, torch.Tensor]:
+    """The tensors Pix2PixModel.preprocess_input hands to the networks (pix2pix_model.py:209-254),
+    NCHW float32 on CPU: one-hot tag/ref label maps [n,2,s,s], 2-channel orientation (use_ig form),
+    images and noise [n,3,s,s].  `unpaired`: the reference label and image are another ellipse and another
+    image (the unpaired stage's loader, train.py:43-46), so that sum(tag - ref) != 0; every other tensor is unchanged."""
+    g = torch.Generator().manual_seed(seed)
+    hair = _ellipses(n, size, g)
     onehot = torch.cat([1 - hair, hair], dim=1)
     theta = torch.rand(n, 1, size, size, generator=g) * math.pi
     orient = torch.cat([torch.sin(2 * theta), torch.cos(2 * theta)], dim=1) * hair
@@ -45,18 +50,27 @@ def synth_batch(n: int, size: int, seed: int = 1234) -> Dict[str, torch.Tensor]:
     out["hole"] = hole * hair
     out["orient_rgb"] = torch.cat([(torch.cos(2 * theta) + 1) / 2, (torch.sin(2 * theta) + 1) / 2,
                                    torch.zeros_like(theta)], dim=1) * hair
+    if unpaired:
+        # a third generator, for the same reason: the default call's tensors do not move
+        g4 = torch.Generator().manual_seed(seed + 15485863)
+        hair_ref = _ellipses(n, size, g4)
+        if float((hair - hair_ref).sum()) == 0:                            # equal areas by chance: take one pixel away
+            hair_ref[:, :, size // 2, size // 2] = 0
+        out["input_ref"] = torch.cat([1 - hair_ref, hair_ref], dim=1)
+        out["image_ref"] = torch.rand(n, 3, size, size, generator=g4) * 2 - 1
+        out["hair_ref"] = hair_ref
     return out
 
 
-def synth_loader_batch(n: int, size: int, seed: int = 1234) -> Dict[str, object]:
+def synth_loader_batch(n: int, size: int, seed: int = 1234, unpaired: bool = False) -> Dict[str, object]:
     """The `data` dict one iteration of the reference's DataLoader yields (data/pix2pix_dataset.py:178-188), i.e. the
     argument of `Pix2PixTrainer.run_generator_one_step`: label index maps [n,1,s,s] (ref == tag), images, the 1-channel
     0..255 orientation map, hole, RGB-coded orientation, noise, instance placeholder and paths.  Same draws as
-    synth_batch (the shared tensors are bit-identical)."""
-    b = synth_batch(n, size, seed)
+    synth_batch (the shared tensors are bit-identical); `unpaired` as there (label_ref / image_ref of another sample)."""
+    b = synth_batch(n, size, seed, unpaired)
     g3 = torch.Generator().manual_seed(seed + 104729)
     orient255 = torch.floor(torch.rand(n, 1, size, size, generator=g3) * 255.0) * b["hair"]
-    return {"label_ref": b["hair"].clone(), "label_tag": b["hair"].clone(), "instance": torch.zeros(n),
+    return {"label_ref": b["hair_ref"] if unpaired else b["hair"].clone(), "label_tag": b["hair"].clone(), "instance": torch.zeros(n),
             "image_ref": b["image_ref"], "image_tag": b["image_tag"], "orient": orient255, "hole": b["hole"],
             "orient_rgb": b["orient_rgb"], "noise": b["noise"], "path": ["synthetic_%d" % i for i in range(n)]}
 

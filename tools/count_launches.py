@@ -1,7 +1,8 @@
 """Launch census of one training step WITHOUT a GPU: torch (aten) ops that would each be a kernel launch on the device, and C-ABI
 calls (= HIP launches), per phase of the step.  Runs the trainer on the contract emulator at a small size -- the launch COUNT of the
 host stack does not depend on the tensor sizes (same code paths), only the dispatch heuristics inside the library do (those are
-counted as one C-ABI call each).     python tools/count_launches.py [--by-op] [--where]
+counted as one C-ABI call each).     python tools/count_launches.py [--by-op] [--where] [--unpaired]
+--unpaired: the step of the unpaired stage (unpairTrain, curr_step = 2: netD2, GAN + ORIENT + hairAvgLab + background) instead.
 
 View-like aten ops (no kernel) are not counted; ops issued INSIDE the emulator (its own arithmetic) are not counted either.
 """
@@ -85,11 +86,14 @@ def main():
     from michigan_amd.synth import synth_batch
     torch.set_num_threads(4)
     census = Census()
-    _cabi.set_backend(CountingBackend(EmulatorBackend(), census))
+    unpaired = "--unpaired" in sys.argv
+    if unpaired:
+        from hair_lab_emulator import HairLabEmulator
+    _cabi.set_backend(CountingBackend(HairLabEmulator() if unpaired else EmulatorBackend(), census))
     torch.manual_seed(0)
-    opt = default_options(ngf=8, ndf=8, crop_size=128, gpu_ids=[], compute_dtype="fp32")
+    opt = default_options(ngf=8, ndf=8, crop_size=128, gpu_ids=[], compute_dtype="fp32", unpairTrain=unpaired, curr_step=2 if unpaired else 1)
     tr = Pix2PixTrainer(opt)
-    data = synth_batch(2, 128, seed=1234)
+    data = synth_batch(2, 128, seed=1234, unpaired=unpaired)
     m = tr.pix2pix_model
 
     def g_step(count):
@@ -102,16 +106,24 @@ def main():
         label = d["input_tag"][:, 1:2]
         ph("G.loss_gan"); lg = m.criterionGAN(pf, True, for_discriminator=False, label=label)
         m._resolve_flag(pending)
-        ph("G.loss_feat"); lf = m.criterionGANFeat(pf, pr, label)
-        ph("G.loss_vgg"); lv = m.criterionVGG(fake, d["image_tag"], label) * opt.lambda_vgg
-        ph("G.loss_orient"); lo = m.criterionOrient(fake, d["orient"], d["input_tag"])[0] * opt.lambda_orient
-        ph("G.loss_sum"); loss = _total({"a": lg, "b": lf, "c": lv, "d": lo})
+        terms = {"a": lg}
+        if not unpaired:
+            ph("G.loss_feat"); terms["b"] = m.criterionGANFeat(pf, pr, label)
+            ph("G.loss_vgg"); terms["c"] = m.criterionVGG(fake, d["image_tag"], label) * opt.lambda_vgg
+        ph("G.loss_orient"); terms["d"] = m.criterionOrient(fake, d["orient"], d["input_tag"])[0] * opt.lambda_orient
+        if unpaired:
+            from michigan_amd import ops
+            ph("G.loss_hair_lab")
+            terms["e"], terms["f"] = ops.hair_lab_losses(fake.permute(0, 2, 3, 1), d["image_ref"], d["input_tag"][:, 1], d["input_ref"][:, 1],
+                                                         d["image_tag"], d["input_tag"][:, 0], ops.HAIR_LAB | ops.HAIR_BACKGROUND)
+        ph("G.loss_sum"); loss = _total(terms)
         ph("G.backward"); loss.backward(); tr._set_d_requires_grad(True)
         ph("G.optimizer"); tr.optimizer_G.step()
 
     def d_step(count):
         ph = (lambda p: setattr(census, "phase", p)) if count else (lambda p: None)
-        ph("D.zero_grad"); tr.optimizer_D.zero_grad()
+        optimizer_d = tr._optimizer_d_in_use()
+        ph("D.zero_grad"); optimizer_d.zero_grad()
         ph("D.preprocess"); d = m.preprocess_input(data); d = m._maybe_inpaint(d)
         ph("D.generator_fwd")
         with torch.no_grad():
@@ -122,7 +134,7 @@ def main():
         ph("D.loss"); l1 = m.criterionGAN(pf, False, for_discriminator=True, label=label); l2 = m.criterionGAN(pr, True, for_discriminator=True, label=label)
         loss = _total({"a": l1, "b": l2})
         ph("D.backward"); loss.backward()
-        ph("D.optimizer"); tr.optimizer_D.step()
+        ph("D.optimizer"); optimizer_d.step()
 
     for it in range(3):                                   # iteration 2 is the steady state (slot layouts, caches recorded)
         random.seed(it)
@@ -134,12 +146,14 @@ def main():
             g_step(False); d_step(False)
     phases = sorted(set(census.aten) | set(census.hip), key=lambda p: (p[0] != "G", p))
     order = ["G.zero_grad", "G.preprocess", "G.generator_fwd", "G.discriminate", "G.loss_gan", "G.loss_feat", "G.loss_vgg", "G.loss_orient",
-             "G.loss_sum", "G.backward", "G.optimizer", "D.zero_grad", "D.preprocess", "D.generator_fwd", "D.discriminate", "D.loss",
+             "G.loss_hair_lab", "G.loss_sum", "G.backward", "G.optimizer", "D.zero_grad", "D.preprocess", "D.generator_fwd", "D.discriminate", "D.loss",
              "D.backward", "D.optimizer"]
     ta = th = 0
     print("%-18s %6s %6s" % ("phase", "aten", "hip"))
     for p in order + [p for p in phases if p not in order]:
         a, h = census.aten.get(p, 0), census.hip.get(p, 0)
+        if p in ("G.loss_feat", "G.loss_vgg", "G.loss_hair_lab") and p not in phases:
+            continue                                      # a term this kind of step does not have
         ta, th = ta + a, th + h
         print("%-18s %6d %6d" % (p, a, h))
     print("%-18s %6d %6d   total %d launches per G+D step" % ("sum", ta, th, ta + th))
