@@ -19,6 +19,7 @@
 // bf16: v_mfma_f32_32x32x16_bf16, fp32 accumulation everywhere, P enters the second product as a hi + lo pair of bf16 values;
 // fp32: v_mfma_f32_32x32x2_f32 (exact fp32 fma, two-level sums over the keys: the parity configuration).
 #include "mg_common.h"
+#include "mg_launch.h"
 
 namespace {
 
@@ -307,7 +308,7 @@ extern "C" int mg_self_attention(const void* q, const void* k, const void* v, vo
     AttnArgs a;
     a.q = q; a.k = k; a.v = v; a.out = out; a.N = N; a.L = L; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MG_BF16) launch_attention<uint16_t>(a, st); else launch_attention<float>(a, st);
+    mg_by_dtype(dtype, [&](auto t) { launch_attention<typename decltype(t)::type>(a, st); });
     MG_CHECK_LAUNCH("mg_self_attention");
     return MG_OK;
 }

@@ -12,6 +12,7 @@
 // The eager spelling is ~40 launches per call, six of them boolean-mask index assignments that synchronise the host; the
 // data is ~50 MB per step at 8 x 512^2, so one coalesced read of each operand is all there is to do here.
 #include "mg_common.h"
+#include "mg_launch.h"
 #include "mg_lab.h"
 
 // No fused multiply-add contraction in this file: a - b of two products that are equal must be exactly 0 (sign(0) = 0 where the
@@ -149,8 +150,8 @@ extern "C" int mg_color_loss_fwd(const void* img, const float* real, int64_t rea
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t HW = (int64_t)H * W;
     const int grid = cl_grid((int64_t)N * HW, CL_BLOCKS);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(color_loss_partial_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, (const uint16_t*)img, real, real_nstride, back, back_nstride, N, HW, C, flags, ws);
-    else hipLaunchKernelGGL(color_loss_partial_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)img, real, real_nstride, back, back_nstride, N, HW, C, flags, ws);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(color_loss_partial_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)img, real, real_nstride, back, back_nstride, N, HW, C, flags, ws); });
     MG_CHECK_LAUNCH("mg_color_loss_fwd");
     const double cnt = (double)N * (double)HW;
     hipLaunchKernelGGL(color_loss_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, grid, 1.0 / (2.0 * cnt), 1.0 / (3.0 * cnt), out);
@@ -167,8 +168,8 @@ extern "C" int mg_color_loss_bwd(const void* img, const float* real, int64_t rea
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t HW = (int64_t)H * W;
     const int grid = cl_grid((int64_t)N * HW, 4096);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(color_loss_bwd_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, (const uint16_t*)img, real, real_nstride, back, back_nstride, g_lab, g_rgb, g_back, N, HW, C, flags, (uint16_t*)dimg);
-    else hipLaunchKernelGGL(color_loss_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)img, real, real_nstride, back, back_nstride, g_lab, g_rgb, g_back, N, HW, C, flags, (float*)dimg);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(color_loss_bwd_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)img, real, real_nstride, back, back_nstride, g_lab, g_rgb, g_back, N, HW, C, flags, (T*)dimg); });
     MG_CHECK_LAUNCH("mg_color_loss_bwd");
     return MG_OK;
 }

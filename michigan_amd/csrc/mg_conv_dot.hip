@@ -9,6 +9,7 @@
 // Results: same products and fp32 accumulation as the tap-list kernel in a different order, bias, activation, one
 // rounding to the storage type.
 #include "mg_conv_common.h"
+#include "mg_launch.h"
 
 
 namespace {
@@ -250,8 +251,8 @@ int launch_conv_dot(ConvK& k, int dtype, hipStream_t st)
     const size_t lds = (size_t)k.ntaps * k.Cout * k.Cin * esz;
     long nblk = ((long)k.ngemm + 3) / 4;
     if (nblk > 256 * 8) nblk = 256 * 8;                                        // persistent: 8 workgroups per CU at most
-    if (dtype == MG_BF16) hipLaunchKernelGGL(conv_dot_kernel<uint16_t>, dim3((unsigned)nblk), dim3(256), lds, st, k);
-    else hipLaunchKernelGGL(conv_dot_kernel<float>, dim3((unsigned)nblk), dim3(256), lds, st, k);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(conv_dot_kernel<T>, dim3((unsigned)nblk), dim3(256), lds, st, k); });
     MG_CHECK_LAUNCH("mg_conv_taps(dot)");
     return MG_OK;
 }

@@ -17,6 +17,7 @@
 //     (one 128-byte line) per pixel.
 // Results are the tap-list kernel's (same products, fp32 accumulation, bias, activation, one rounding to bf16).
 #include "mg_conv_common.h"
+#include "mg_launch.h"
 #include "mg_wgrad_common.h"
 
 
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_thin_kernel(const ConvK d, con
         }
     }
 
-    const float neg = d.act == MG_ACT_NONE ? 1.f : (d.act == MG_ACT_RELU ? 0.f : d.slope);
+    const float neg = mg_neg_slope(d.act, d.slope);
     const bool relu = d.act == MG_ACT_RELU;
     const uint16_t* __restrict__ In = reinterpret_cast<const uint16_t*>(d.in);
     unsigned char* __restrict__ Out = reinterpret_cast<unsigned char*>(d.out);
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void conv_thin_taps_kernel(const ConvK d, c
             *reinterpret_cast<uint4*>(wl + i * 16) = v;
         }
     }
-    const float neg = d.act == MG_ACT_NONE ? 1.f : (d.act == MG_ACT_RELU ? 0.f : d.slope);
+    const float neg = mg_neg_slope(d.act, d.slope);
     const bool relu = d.act == MG_ACT_RELU;
     const uint16_t* __restrict__ In = reinterpret_cast<const uint16_t*>(d.in);
     unsigned char* __restrict__ Out = reinterpret_cast<unsigned char*>(d.out);

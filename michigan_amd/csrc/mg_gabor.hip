@@ -9,6 +9,7 @@
 // conf_raw[N,H,W] (fp32) and idx[N,H,W] (u8) reach HBM.  The backward is the gather form of the adjoint:
 // dgray[p'] = sum_{p in 17x17 around p'} g[p] * K_{idx[p]}(p' - p), then the gray weights back to RGB.
 #include "mg_common.h"
+#include "mg_launch.h"
 
 namespace {
 
@@ -149,8 +150,8 @@ extern "C" int mg_gabor_argmax_fwd(const void* img, const float* bank, float* co
     MG_CHECK_ARG(img && bank && conf && idx, "mg_gabor_argmax_fwd: null pointer");
     const int tx = (W + TGW - 1) / TGW, ty = (H + TGH - 1) / TGH;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(gabor_fwd_kernel<uint16_t>, dim3(N * tx * ty), dim3(256), 0, st, (const uint16_t*)img, bank, conf, idx, N, H, W, C, tx, ty);
-    else hipLaunchKernelGGL(gabor_fwd_kernel<float>, dim3(N * tx * ty), dim3(256), 0, st, (const float*)img, bank, conf, idx, N, H, W, C, tx, ty);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(gabor_fwd_kernel<T>, dim3(N * tx * ty), dim3(256), 0, st, (const T*)img, bank, conf, idx, N, H, W, C, tx, ty); });
     MG_CHECK_LAUNCH("mg_gabor_argmax_fwd");
     return MG_OK;
 }
@@ -162,8 +163,8 @@ extern "C" int mg_gabor_argmax_bwd(const float* dconf, const uint8_t* idx, const
     MG_CHECK_ARG(dconf && idx && bank && dimg, "mg_gabor_argmax_bwd: null pointer");
     const int tx = (W + TGW - 1) / TGW, ty = (H + TGH - 1) / TGH;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(gabor_bwd_kernel<uint16_t>, dim3(N * tx * ty), dim3(256), 0, st, dconf, idx, bank, (uint16_t*)dimg, N, H, W, C, tx, ty);
-    else hipLaunchKernelGGL(gabor_bwd_kernel<float>, dim3(N * tx * ty), dim3(256), 0, st, dconf, idx, bank, (float*)dimg, N, H, W, C, tx, ty);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(gabor_bwd_kernel<T>, dim3(N * tx * ty), dim3(256), 0, st, dconf, idx, bank, (T*)dimg, N, H, W, C, tx, ty); });
     MG_CHECK_LAUNCH("mg_gabor_argmax_bwd");
     return MG_OK;
 }

@@ -18,6 +18,7 @@
 //                            (sin 2a, cos 2a) of the winning filter, masked L1 against the label and the confidence term, forward
 //                            (two-stage deterministic sums) and backward (d/d confidence response) -- ~45 launches per step before.
 #include "mg_common.h"
+#include "mg_launch.h"
 
 namespace {
 
@@ -293,8 +294,6 @@ __global__ __launch_bounds__(256) void masked_mean_fill_kernel(const T* __restri
     }
 }
 
-inline int ew_grid(int64_t n, int thr = 256, int cap = 4096) { const int64_t g = (n + thr - 1) / thr; return (int)(g > cap ? cap : (g < 1 ? 1 : g)); }
-
 }  // namespace
 
 extern "C" int mg_nearest_pyramid(const mg_pyramid_desc* d, void* stream)
@@ -310,8 +309,8 @@ extern "C" int mg_nearest_pyramid(const mg_pyramid_desc* d, void* stream)
     }
     for (int c = 0; c < d->nplanes; ++c) MG_CHECK_ARG(d->plane[c], "mg_nearest_pyramid: null plane %d", c);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d->dtype == MG_BF16) hipLaunchKernelGGL(nearest_pyramid_kernel<uint16_t>, dim3(ew_grid(total)), dim3(256), 0, st, *d, total);
-    else hipLaunchKernelGGL(nearest_pyramid_kernel<float>, dim3(ew_grid(total)), dim3(256), 0, st, *d, total);
+    mg_by_dtype(d->dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(nearest_pyramid_kernel<T>, dim3(mg_ew_grid(total, 4096)), dim3(256), 0, st, *d, total); });
     MG_CHECK_LAUNCH("mg_nearest_pyramid");
     return MG_OK;
 }
@@ -322,7 +321,7 @@ extern "C" int mg_pconv_mask(const float* mask_in, int32_t N, int32_t H, int32_t
     MG_CHECK_ARG(mask_in && scale && upd, "mg_pconv_mask: null pointer");
     MG_CHECK_ARG(N > 0 && H > 0 && W > 0 && k >= 1 && s >= 1 && p >= 0 && H + 2 * p >= k && W + 2 * p >= k, "mg_pconv_mask: bad geometry");
     const int h = (H + 2 * p - k) / s + 1, w = (W + 2 * p - k) / s + 1;
-    hipLaunchKernelGGL(pconv_mask_kernel, dim3(ew_grid((int64_t)N * h * w)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(pconv_mask_kernel, dim3(mg_ew_grid((int64_t)N * h * w, 4096)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        mask_in, N, H, W, k, s, p, h, w, scale, upd);
     MG_CHECK_LAUNCH("mg_pconv_mask");
     return MG_OK;
@@ -335,9 +334,9 @@ extern "C" int mg_pixel_affine(const void* x, const float* a, const float* bias,
     MG_CHECK_ARG((dtype == MG_F32 || dtype == MG_BF16) && P > 0 && C > 0 && (C & 3) == 0, "mg_pixel_affine: C must be a positive multiple of 4");
     MG_CHECK_ARG((bias == nullptr) == (b == nullptr), "mg_pixel_affine: bias and b come together");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int grid = ew_grid(P * (C >> 2));
-    if (dtype == MG_BF16) hipLaunchKernelGGL(pixel_affine_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, (const uint16_t*)x, a, bias, b, P, C, (uint16_t*)y);
-    else hipLaunchKernelGGL(pixel_affine_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, a, bias, b, P, C, (float*)y);
+    const int grid = mg_ew_grid(P * (C >> 2), 4096);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pixel_affine_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)x, a, bias, b, P, C, (T*)y); });
     MG_CHECK_LAUNCH("mg_pixel_affine");
     return MG_OK;
 }
@@ -350,8 +349,8 @@ extern "C" int mg_bg_compose(const float* image, const float* noise, const float
     MG_CHECK_ARG(mode == 1 || (mode == 0 && k >= 1 && (k & 1) == 1 && k / 2 <= BG_RMAX), "mg_bg_compose: the dilation window must be odd and <= %d", 2 * BG_RMAX + 1);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((W + BG_T - 1) / BG_T, (H + BG_T - 1) / BG_T, N);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(bg_compose_kernel<uint16_t>, grid, dim3(256), 0, st, image, noise, hair, hair_nstride, H, W, k, mode, (uint16_t*)inp, back);
-    else hipLaunchKernelGGL(bg_compose_kernel<float>, grid, dim3(256), 0, st, image, noise, hair, hair_nstride, H, W, k, mode, (float*)inp, back);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(bg_compose_kernel<T>, grid, dim3(256), 0, st, image, noise, hair, hair_nstride, H, W, k, mode, (T*)inp, back); });
     MG_CHECK_LAUNCH("mg_bg_compose");
     return MG_OK;
 }
@@ -362,7 +361,7 @@ extern "C" int mg_orient_loss_fwd(const float* conf_raw, const uint8_t* idx, con
     MG_CHECK_ARG(conf_raw && idx && label && hair && out && ws, "mg_orient_loss_fwd: null pointer");
     MG_CHECK_ARG((label_ch == 1 || label_ch == 2) && N > 0 && HW > 0, "mg_orient_loss_fwd: bad geometry");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int grid = ew_grid((int64_t)N * HW, 256, 1024);
+    const int grid = mg_ew_grid((int64_t)N * HW, 1024);
     hipLaunchKernelGGL(orient_loss_partial_kernel, dim3(grid), dim3(256), 0, st, conf_raw, idx, label, label_ch, label_nstride, hair, hair_nstride, N, HW, ws);
     MG_CHECK_LAUNCH("mg_orient_loss_fwd");
     hipLaunchKernelGGL(orient_loss_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, grid, 1.0 / (2.0 * (double)N * (double)HW), out);
@@ -376,7 +375,7 @@ extern "C" int mg_orient_loss_bwd(const float* conf_raw, const uint8_t* idx, con
 {
     MG_CHECK_ARG(conf_raw && idx && label && hair && fwd_out && dconf, "mg_orient_loss_bwd: null pointer");
     MG_CHECK_ARG((label_ch == 1 || label_ch == 2) && N > 0 && HW > 0, "mg_orient_loss_bwd: bad geometry");
-    hipLaunchKernelGGL(orient_loss_bwd_kernel, dim3(ew_grid((int64_t)N * HW)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(orient_loss_bwd_kernel, dim3(mg_ew_grid((int64_t)N * HW, 4096)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        conf_raw, idx, label, label_ch, label_nstride, hair, hair_nstride, g_orient, g_conf, fwd_out, N, HW, dconf);
     MG_CHECK_LAUNCH("mg_orient_loss_bwd");
     return MG_OK;
@@ -389,8 +388,8 @@ extern "C" int mg_masked_mean_fill(const void* x, const float* w_in, const float
     MG_CHECK_ARG((dtype == MG_F32 || dtype == MG_BF16) && N > 0 && P > 0 && C > 0 && (C & 3) == 0, "mg_masked_mean_fill: bad geometry");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((C / 4 + 15) / 16, N);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(masked_mean_fill_kernel<uint16_t>, grid, dim3(256), 0, st, (const uint16_t*)x, w_in, w_out, w_norm, P, C, out);
-    else hipLaunchKernelGGL(masked_mean_fill_kernel<float>, grid, dim3(256), 0, st, (const float*)x, w_in, w_out, w_norm, P, C, out);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(masked_mean_fill_kernel<T>, grid, dim3(256), 0, st, (const T*)x, w_in, w_out, w_norm, P, C, out); });
     MG_CHECK_LAUNCH("mg_masked_mean_fill");
     return MG_OK;
 }

@@ -13,6 +13,7 @@
 // What is provably zero is not read: img only where m_f != 0 (bit 0) or m_b != 0 (bit 1), ref only where m_r != 0, tgt only where
 // m_b != 0 -- with a one-hot label every pixel takes exactly one of the two branches.
 #include "mg_common.h"
+#include "mg_launch.h"
 #include "mg_lab.h"
 
 #pragma clang fp contract(off)
@@ -193,8 +194,8 @@ extern "C" int mg_hair_lab_fwd(const void* img, const float* ref, int64_t ref_ns
     const int64_t HW = (int64_t)H * W;
     const int bps = hl_bps(HW, N, HL_BLOCKS);
     const dim3 grid(bps, N);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(hair_lab_partial_kernel<uint16_t>, grid, dim3(256), 0, st, (const uint16_t*)img, ref, ref_nstride, hair_tag, hair_tag_nstride, hair_ref, hair_ref_nstride, tgt, tgt_nstride, back, back_nstride, N, HW, C, flags, ws);
-    else hipLaunchKernelGGL(hair_lab_partial_kernel<float>, grid, dim3(256), 0, st, (const float*)img, ref, ref_nstride, hair_tag, hair_tag_nstride, hair_ref, hair_ref_nstride, tgt, tgt_nstride, back, back_nstride, N, HW, C, flags, ws);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(hair_lab_partial_kernel<T>, grid, dim3(256), 0, st, (const T*)img, ref, ref_nstride, hair_tag, hair_tag_nstride, hair_ref, hair_ref_nstride, tgt, tgt_nstride, back, back_nstride, N, HW, C, flags, ws); });
     MG_CHECK_LAUNCH("mg_hair_lab_fwd");
     hipLaunchKernelGGL(hair_lab_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, N, bps, flags, 1.0 / (2.0 * (double)N), 1.0 / (3.0 * (double)N * (double)HW), stats, out);
     MG_CHECK_LAUNCH("mg_hair_lab_fwd(final)");
@@ -211,8 +212,8 @@ extern "C" int mg_hair_lab_bwd(const void* img, const float* hair_tag, int64_t h
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t HW = (int64_t)H * W;
     const dim3 grid(hl_bps(HW, N, 4096), N);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(hair_lab_bwd_kernel<uint16_t>, grid, dim3(256), 0, st, (const uint16_t*)img, hair_tag, hair_tag_nstride, tgt, tgt_nstride, back, back_nstride, stats, g_hair, g_back, N, HW, C, flags, (uint16_t*)dimg);
-    else hipLaunchKernelGGL(hair_lab_bwd_kernel<float>, grid, dim3(256), 0, st, (const float*)img, hair_tag, hair_tag_nstride, tgt, tgt_nstride, back, back_nstride, stats, g_hair, g_back, N, HW, C, flags, (float*)dimg);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(hair_lab_bwd_kernel<T>, grid, dim3(256), 0, st, (const T*)img, hair_tag, hair_tag_nstride, tgt, tgt_nstride, back, back_nstride, stats, g_hair, g_back, N, HW, C, flags, (T*)dimg); });
     MG_CHECK_LAUNCH("mg_hair_lab_bwd");
     return MG_OK;
 }

@@ -1,0 +1,28 @@
+// Host-side launch helpers shared by the streaming kernel files (include after mg_common.h): the dtype dispatch, the block size
+// and grid of a grid-stride pass, and the activation's slope factor.  Prefixed: mg_conv_common.h and mg_inputs.hip keep an
+// NTHR / ew_grid of their own.
+#pragma once
+#include "mg_common.h"
+
+constexpr int MG_NTHR = 256;
+// blocks of MG_NTHR threads for n work items, at least one and at most `cap` (the kernel strides over the rest)
+static inline int mg_ew_grid(int64_t n, int cap) { int64_t b = (n + MG_NTHR - 1) / MG_NTHR; return (int)(b > cap ? cap : (b < 1 ? 1 : b)); }
+
+#define MG_GRID_STRIDE(i, n) \
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
+
+// f(tag) with tag::type = uint16_t (MG_BF16) or float (anything else: the entry point has checked dtype).  A call site is
+//     mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type; hipLaunchKernelGGL(kern<T>, ..., (const T*)x, ...); });
+// so the argument list of a launch exists once.  The bf16 branch comes first: kernels are emitted in order of first use.
+template <typename T> struct mg_dtype_tag { using type = T; };
+template <typename F> static inline auto mg_by_dtype(int dtype, F&& f)
+{
+    if (dtype == MG_BF16) return f(mg_dtype_tag<uint16_t>{});
+    return f(mg_dtype_tag<float>{});
+}
+
+// derivative factor of NONE / RELU / LRELU through the output: y > 0 ? 1 : mg_neg_slope(act, slope)
+__host__ __device__ static __forceinline__ float mg_neg_slope(int act, float slope)
+{
+    return act == MG_ACT_NONE ? 1.f : (act == MG_ACT_RELU ? 0.f : slope);
+}

@@ -13,6 +13,7 @@
 //   hinge_bwd_kernel         dx = -g / n * f'(x) * w in the logits' dtype.
 // Index work on tiny maps: one thread per element, no LDS tiling needed (each 67x67 map is 18 KiB).
 #include "mg_common.h"
+#include "mg_launch.h"
 
 namespace {
 
@@ -106,8 +107,8 @@ extern "C" int mg_hinge_fwd(const void* x, const float* weight, int32_t dtype, i
     MG_CHECK_ARG(x && out, "mg_hinge_fwd: null pointer");
     MG_CHECK_ARG((dtype == MG_F32 || dtype == MG_BF16) && n > 0 && mode >= 0 && mode <= 2, "mg_hinge_fwd: bad dtype / size / mode");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(hinge_fwd_kernel<uint16_t>, dim3(1), dim3(1024), 0, st, (const uint16_t*)x, weight, n, mode, out);
-    else hipLaunchKernelGGL(hinge_fwd_kernel<float>, dim3(1), dim3(1024), 0, st, (const float*)x, weight, n, mode, out);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(hinge_fwd_kernel<T>, dim3(1), dim3(1024), 0, st, (const T*)x, weight, n, mode, out); });
     MG_CHECK_LAUNCH("mg_hinge_fwd");
     return MG_OK;
 }
@@ -119,8 +120,8 @@ extern "C" int mg_hinge_bwd(const void* x, const float* weight, const float* g, 
     MG_CHECK_ARG((dtype == MG_F32 || dtype == MG_BF16) && n > 0 && mode >= 0 && mode <= 2, "mg_hinge_bwd: bad dtype / size / mode");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int grid = cdiv(n, 256) > 1024 ? 1024 : cdiv(n, 256);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(hinge_bwd_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, (const uint16_t*)x, weight, g, n, mode, (uint16_t*)dx);
-    else hipLaunchKernelGGL(hinge_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, weight, g, n, mode, (float*)dx);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(hinge_bwd_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)x, weight, g, n, mode, (T*)dx); });
     MG_CHECK_LAUNCH("mg_hinge_bwd");
     return MG_OK;
 }

@@ -17,13 +17,12 @@
 // sample pivot makes the partial sums grow like n |k| instead of sqrt(n) sigma.  Per-thread fp64 accumulation (no pivot needed) was
 // measured too: same results, stats_stage1_vec 17.8 -> 21.7 us per launch (+0.24 ms per step), not kept.
 #include "mg_common.h"
+#include "mg_launch.h"
 #include "mg_options.h"
 #include <type_traits>
 
 
 namespace {
-
-constexpr int NTHR = 256;
 
 struct StatGeom { int tpr; int rpb; int nchunks; int64_t chunk; };
 
@@ -31,8 +30,8 @@ static inline StatGeom stat_geom(int G, int64_t P, int C)
 {
     StatGeom g;
     const int c4 = C / 4;
-    g.tpr = c4 < NTHR ? c4 : NTHR;
-    g.rpb = NTHR / g.tpr;
+    g.tpr = c4 < MG_NTHR ? c4 : MG_NTHR;
+    g.rpb = MG_NTHR / g.tpr;
     // enough stage-1 blocks to fill 256 CUs a few times over (G groups share the budget), but at
     // least 16 rows per thread and at most 512 partials per group for the stage-2 tree.
     int64_t want = (1536 + G - 1) / G;
@@ -45,15 +44,70 @@ static inline StatGeom stat_geom(int G, int64_t P, int C)
     return g;
 }
 
+// blocks of `rows` channel-resident thread rows with `pix` pixels in flight each, at most 4096 over the G groups
+static inline int pix_grid(int64_t P, int rows, int pix, int G)
+{
+    int64_t b = (P + (int64_t)rows * pix - 1) / ((int64_t)rows * pix);
+    const int64_t cap = (4096 + G - 1) / G;
+    if (b > cap) b = cap;
+    return (int)(b < 1 ? 1 : b);
+}
+
+// element offset of channel c of the half-resolution source pixel that full-resolution pixel q of [N, H, W] reads through a
+// nearest 2x upsample
+__device__ __forceinline__ size_t up_src_offset(int q, int H, int W, int C, int c)
+{
+    const int n = q / (H * W), rem = q - n * (H * W);
+    const int yy = rem / W, xx = rem - yy * W;
+    return ((size_t)(n * (H >> 1) + (yy >> 1)) * (W >> 1) + (xx >> 1)) * C + c;
+}
+
+// a + this thread's share of column p[0] of the [nchunks][C2] partials: chunks k, k + 8, ... in fp64, fixed order.
+// Eight independent loads in flight per thread (the trip count is a runtime value: without the explicit batch the loop was a
+// chain of ~64 dependent L2 round trips, 10.6 us per launch, 99 launches per step); same summation order as the plain loop
+__device__ __forceinline__ double chunk_sum_f64(double a, const float* p, int k, int nchunks, int C2)
+{
+    for (; k + 56 < nchunks; k += 64) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = p[(size_t)(k + 8 * j) * C2];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a += (double)v[j];
+    }
+    for (; k < nchunks; k += 8) a += (double)p[(size_t)k * C2];
+    return a;
+}
+
+// sums of one channel -> mean / rstd (fp64 inside) and the optional running-statistics update of channel c: the one copy of this
+// arithmetic, so mg_channel_stats_finalize is bit-identical to mg_channel_stats + mg_norm_finalize by construction.  at() is the
+// channel's index into mean / rstd, a callable so that it is formed at the stores, where each caller had it: both kernels keep
+// their instructions
+template <typename Index>
+__device__ __forceinline__ void finalize_channel(double s, double ss, double count, float eps, float momentum,
+                                                 float* running_mean, float* running_var, int c,
+                                                 float* mean, float* rstd, Index&& at)
+{
+    const double m = s / count;
+    double var = ss / count - m * m;
+    if (var < 0.0) var = 0.0;
+    mean[at()] = (float)m;
+    rstd[at()] = (float)(1.0 / sqrt(var + (double)eps));
+    if (running_mean) {
+        const double unbiased = var * (count / (count > 1.0 ? count - 1.0 : 1.0));
+        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
+        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+    }
+}
+
 // MODE 0: plain (sum x, sum x^2).  MODE 1: norm backward (sum dxhat, sum dxhat*xhat [+ dgb]).
 template <typename T, int MODE, bool HAS_H = true>
-__global__ __launch_bounds__(NTHR) void reduce_stage1(
+__global__ __launch_bounds__(MG_NTHR) void reduce_stage1(
     const T* __restrict__ x, const T* __restrict__ dh, const T* __restrict__ h, const T* __restrict__ g1,
     const float* __restrict__ mean, const float* __restrict__ rstd, T* __restrict__ dgb,
     float* __restrict__ partial, int64_t P, int C, int tpr, int rpb, int64_t chunk, int act, float slope,
     int up = 0, int H = 0, int W = 0)
 {
-    __shared__ float red[NTHR * 8];
+    __shared__ float red[MG_NTHR * 8];
     const int tid = threadIdx.x;
     const int g = blockIdx.y, ck = blockIdx.x, nchunks = gridDim.x;
     const int c4 = C / 4;
@@ -80,11 +134,7 @@ __global__ __launch_bounds__(NTHR) void reduce_stage1(
             for (int64_t p = p0 + tr; p < p1; p += rpb) {
                 const size_t o = ((size_t)g * P + p) * C + c;
                 size_t ox = o;
-                if (MODE == 1 && up) {                       // x is the half-resolution source of a nearest 2x upsample (G == 1)
-                    const int pp = (int)p, n = pp / (H * W), rem = pp - n * (H * W);
-                    const int yy = rem / W, xx = rem - yy * W;
-                    ox = ((size_t)(n * (H >> 1) + (yy >> 1)) * (W >> 1) + (xx >> 1)) * C + c;
-                }
+                if (MODE == 1 && up) ox = up_src_offset((int)p, H, W, C, c);      // x is the half-resolution source of a nearest 2x upsample (G == 1)
                 const f32x4_t xv = ET<T>::load4(x + ox);
                 if (MODE == 0) {
 #pragma unroll
@@ -141,20 +191,7 @@ __global__ __launch_bounds__(256) void reduce_stage2(const float* __restrict__ p
     const int i = blockIdx.x * 32 + cl;
     const int g = blockIdx.y;
     double a = 0.0;
-    if (i < C2) {
-        const float* p = partial + (size_t)g * nchunks * C2 + i;
-        // eight independent loads in flight per thread (the trip count is a runtime value: without the explicit batch the loop was a
-        // chain of ~64 dependent L2 round trips, 10.6 us per launch, 99 launches per step); same summation order as before
-        int k = kk;
-        for (; k + 56 < nchunks; k += 64) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = p[(size_t)(k + 8 * j) * C2];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a += (double)v[j];
-        }
-        for (; k < nchunks; k += 8) a += (double)p[(size_t)k * C2];
-    }
+    if (i < C2) a = chunk_sum_f64(a, partial + (size_t)g * nchunks * C2 + i, kk, nchunks, C2);
     red[threadIdx.x] = a;
     __syncthreads();
     if (kk == 0 && i < C2) {
@@ -256,25 +293,28 @@ template <> struct VT<uint16_t> {
     }
 };
 
+// f(std::true_type) or f(std::false_type): a runtime flag as a template argument (the true branch first, like mg_by_dtype)
+template <typename F> static inline void by_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+
 template <typename T> static inline bool vec_geom_ok(int C)
 {
     constexpr int VEC = VT<T>::VEC;
     if (C % VEC) return false;
     const int cv = C / VEC;
-    return cv <= NTHR && NTHR % cv == 0;
+    return cv <= MG_NTHR && MG_NTHR % cv == 0;
 }
 
 // derivative factor of NONE / RELU / LRELU through the output: y > 0 ? 1 : neg
 __device__ __forceinline__ float act_factor(float y, float neg) { return y > 0.f ? 1.f : neg; }
 
 template <typename T, int PIX>
-__global__ __launch_bounds__(NTHR) void norm_bwd_apply_vec(const T* __restrict__ dh, const T* __restrict__ h, const T* __restrict__ x,
+__global__ __launch_bounds__(MG_NTHR) void norm_bwd_apply_vec(const T* __restrict__ dh, const T* __restrict__ h, const T* __restrict__ x,
                                                          const T* __restrict__ g1, T* __restrict__ dx, int64_t P, int C,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          const float* __restrict__ s1, const float* __restrict__ s2, int sgs, float sscale, float neg)
 {
     constexpr int VEC = VT<T>::VEC;
-    const int cv = C / VEC, rows = NTHR / cv;
+    const int cv = C / VEC, rows = MG_NTHR / cv;
     const int tq = threadIdx.x % cv, tr = threadIdx.x / cv;
     const int g = blockIdx.y, c = tq * VEC;
     float m[VEC], r[VEC], c1[VEC], c2[VEC];
@@ -315,12 +355,12 @@ __global__ __launch_bounds__(NTHR) void norm_bwd_apply_vec(const T* __restrict__
 }
 
 template <typename T, int PIX>
-__global__ __launch_bounds__(NTHR) void norm_act_fwd_vec(const T* __restrict__ x, T* __restrict__ y, int64_t P, int C,
+__global__ __launch_bounds__(MG_NTHR) void norm_act_fwd_vec(const T* __restrict__ x, T* __restrict__ y, int64_t P, int C,
                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
                                                        float neg, bool relu, const T* __restrict__ resid)
 {
     constexpr int VEC = VT<T>::VEC;
-    const int cv = C / VEC, rows = NTHR / cv;
+    const int cv = C / VEC, rows = MG_NTHR / cv;
     const int tq = threadIdx.x % cv, tr = threadIdx.x / cv;
     const int g = blockIdx.y, c = tq * VEC;
     float m[VEC], r[VEC];
@@ -355,11 +395,11 @@ __global__ __launch_bounds__(NTHR) void norm_act_fwd_vec(const T* __restrict__ x
 
 // stage 1 of the plain statistics (sum x, sum x^2) with the same chunking / partial layout as reduce_stage1<T, 0>
 template <typename T, int PIX>
-__global__ __launch_bounds__(NTHR) void stats_stage1_vec(const T* __restrict__ x, float* __restrict__ partial, int64_t P, int C, int64_t chunk, int shift)
+__global__ __launch_bounds__(MG_NTHR) void stats_stage1_vec(const T* __restrict__ x, float* __restrict__ partial, int64_t P, int C, int64_t chunk, int shift)
 {
     constexpr int VEC = VT<T>::VEC;
-    __shared__ float red[NTHR * 2 * VEC];
-    const int cv = C / VEC, rows = NTHR / cv;
+    __shared__ float red[MG_NTHR * 2 * VEC];
+    const int cv = C / VEC, rows = MG_NTHR / cv;
     const int tq = threadIdx.x % cv, tr = threadIdx.x / cv;
     const int g = blockIdx.y, ck = blockIdx.x, nchunks = gridDim.x, c = tq * VEC;
     const int64_t p0 = (int64_t)ck * chunk;
@@ -411,13 +451,13 @@ __global__ __launch_bounds__(NTHR) void stats_stage1_vec(const T* __restrict__ x
 // vector -- the quad kernel moved its four input streams in 8-byte pieces at 4.4 TB/s and was the largest non-MFMA kernel of the step.
 // Same chunking and partial layout; `act` is NONE / RELU / LRELU only (neg = 1 / 0 / slope), TANH stays on the quad kernel.
 template <typename T, int PIX, bool HAS_H, bool UP>
-__global__ __launch_bounds__(NTHR) void bwd_stage1_vec(const T* __restrict__ x, const T* __restrict__ dh, const T* __restrict__ h, const T* __restrict__ g1,
+__global__ __launch_bounds__(MG_NTHR) void bwd_stage1_vec(const T* __restrict__ x, const T* __restrict__ dh, const T* __restrict__ h, const T* __restrict__ g1,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd, T* __restrict__ dgb,
                                                      float* __restrict__ partial, int64_t P, int C, int64_t chunk, float neg, int H, int W)
 {
     constexpr int VEC = VT<T>::VEC;
-    __shared__ float red[NTHR * 2 * VEC];
-    const int cv = C / VEC, rows = NTHR / cv;
+    __shared__ float red[MG_NTHR * 2 * VEC];
+    const int cv = C / VEC, rows = MG_NTHR / cv;
     const int tq = threadIdx.x % cv, tr = threadIdx.x / cv;
     const int g = blockIdx.y, ck = blockIdx.x, nchunks = gridDim.x, c = tq * VEC;
     const int Cr2 = 2 * ((C + 31) / 32) * 32;
@@ -435,11 +475,7 @@ __global__ __launch_bounds__(NTHR) void bwd_stage1_vec(const T* __restrict__ x, 
             const int64_t p = pp + (int64_t)k * rows;
             if (p < p1) {
                 size_t ox = base + (size_t)p * C;
-                if (UP) {                                        // x is the half-resolution source of a nearest 2x upsample (G == 1)
-                    const int q = (int)p, n = q / (H * W), rem = q - n * (H * W);
-                    const int yy = rem / W, xx = rem - yy * W;
-                    ox = ((size_t)(n * (H >> 1) + (yy >> 1)) * (W >> 1) + (xx >> 1)) * C + c;
-                }
+                if (UP) ox = up_src_offset((int)p, H, W, C, c);       // x is the half-resolution source of a nearest 2x upsample (G == 1)
                 VT<T>::load(x + ox, xv[k]);
                 VT<T>::load(dh + base + (size_t)p * C, dv[k]);
                 if (HAS_H) VT<T>::load(h + base + (size_t)p * C, hv[k]);
@@ -483,14 +519,6 @@ __global__ __launch_bounds__(NTHR) void bwd_stage1_vec(const T* __restrict__ x, 
     }
 }
 
-static inline int pix_grid(int64_t P, int rows, int pix, int G)
-{
-    int64_t b = (P + (int64_t)rows * pix - 1) / ((int64_t)rows * pix);
-    const int64_t cap = (4096 + G - 1) / G;
-    if (b > cap) b = cap;
-    return (int)(b < 1 ? 1 : b);
-}
-
 // sums[g][2][C] (+ element count) -> mean / rstd (fp64 inside), optional running-statistics update (G == 1):
 // replaces a dozen [C]-sized eager ops per normalisation layer.
 __global__ void norm_finalize_kernel(const double* __restrict__ sums, int G, int C, double count, float eps, float momentum,
@@ -501,19 +529,8 @@ __global__ void norm_finalize_kernel(const double* __restrict__ sums, int G, int
     if (i >= G * C) return;
     const int g = i / C, c = i - g * C;
     const double s = sums[((size_t)g * 2) * C + c], ss = sums[((size_t)g * 2 + 1) * C + c];
-    const double m = s / count;
-    double var = ss / count - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[i] = (float)m;
-    rstd[i] = (float)(1.0 / sqrt(var + (double)eps));
-    if (running_mean) {
-        const double unbiased = var * (count / (count > 1.0 ? count - 1.0 : 1.0));
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    }
+    finalize_channel(s, ss, count, eps, momentum, running_mean, running_var, c, mean, rstd, [&] { return i; });
 }
-
-static inline int ew_grid(int64_t n) { int64_t b = (n + NTHR - 1) / NTHR; return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
 
 // Input gradient of batch norm for up to TWO consumers that normalise the same x (SPADE norm_0 / norm_s of a block with a learned
 // shortcut, architecture.py:68-70,79), optionally through a nearest 2x upsample of x (generator.py:166-207):
@@ -522,10 +539,10 @@ static inline int ew_grid(int64_t n) { int64_t b = (n + NTHR - 1) / NTHR; return
 // One pass instead of two applies + autograd's add of their results + the upsample's 2x2 adjoint: x is read once at its own
 // resolution and dx written once at its own resolution.  Channel-resident threads like norm_bwd_apply_vec.
 template <typename T, int NB, bool UP>
-__global__ __launch_bounds__(NTHR) void norm_bwd_apply2_vec(const mg_norm_apply2_desc d, float neg0, float neg1)
+__global__ __launch_bounds__(MG_NTHR) void norm_bwd_apply2_vec(const mg_norm_apply2_desc d, float neg0, float neg1)
 {
     constexpr int VEC = VT<T>::VEC;
-    const int C = d.C, cv = C / VEC, rows = NTHR / cv;
+    const int C = d.C, cv = C / VEC, rows = MG_NTHR / cv;
     const int tq = threadIdx.x % cv, tr = threadIdx.x / cv;
     const int c = tq * VEC;
     const T* dh0 = (const T*)d.dh[0]; const T* h0 = (const T*)d.h[0]; const T* g0 = (const T*)d.g1[0];
@@ -607,20 +624,7 @@ __global__ __launch_bounds__(256) void stats_stage2(const float* __restrict__ pa
     const int C2 = 2 * C;
     const int i = (cl >> 4) * C + c;                            // column of the [sum | sum of squares] vector
     double a = 0.0;
-    if (c < C) {
-        const float* p = partial + (size_t)g * nchunks * C2 + i;
-        // eight independent loads in flight per thread (the trip count is a runtime value: without the explicit batch the loop was a
-        // chain of ~64 dependent L2 round trips)
-        int k = kk;
-        for (; k + 56 < nchunks; k += 64) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = p[(size_t)(k + 8 * j) * C2];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a += (double)v[j];
-        }
-        for (; k < nchunks; k += 8) a += (double)p[(size_t)k * C2];
-    }
+    if (c < C) a = chunk_sum_f64(a, partial + (size_t)g * nchunks * C2 + i, kk, nchunks, C2);
     red[threadIdx.x] = a;
     __syncthreads();
     if (kk == 0) {
@@ -636,18 +640,7 @@ __global__ __launch_bounds__(256) void stats_stage2(const float* __restrict__ pa
         const double ss = (ssh + 2.0 * kv * sh + n * kv * kv) * sum_scale;
         sums[(size_t)g * C2 + c] = s;
         sums[(size_t)g * C2 + C + c] = ss;
-        if (FIN) {
-            const double m = s / count;
-            double var = ss / count - m * m;
-            if (var < 0.0) var = 0.0;
-            mean[(size_t)g * C + c] = (float)m;
-            rstd[(size_t)g * C + c] = (float)(1.0 / sqrt(var + (double)eps));
-            if (running_mean) {
-                const double unbiased = var * (count / (count > 1.0 ? count - 1.0 : 1.0));
-                running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-                running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-            }
-        }
+        if (FIN) finalize_channel(s, ss, count, eps, momentum, running_mean, running_var, c, mean, rstd, [&] { return (size_t)g * C + c; });
     }
 }
 
@@ -659,9 +652,9 @@ int run_stats(const void* x, int G, int64_t P, int C, int shift, double* sums, v
     const StatGeom sg = stat_geom(G, P, C);
     dim3 grid(sg.nchunks, G);
     if (vec_geom_ok<T>(C))
-        hipLaunchKernelGGL((stats_stage1_vec<T, 4>), grid, dim3(NTHR), 0, st, (const T*)x, (float*)partial, P, C, sg.chunk, shift);
+        hipLaunchKernelGGL((stats_stage1_vec<T, 4>), grid, dim3(MG_NTHR), 0, st, (const T*)x, (float*)partial, P, C, sg.chunk, shift);
     else
-        hipLaunchKernelGGL((reduce_stage1<T, 0, true>), grid, dim3(NTHR), 0, st, (const T*)x, (const T*)nullptr, (const T*)nullptr, (const T*)nullptr,
+        hipLaunchKernelGGL((reduce_stage1<T, 0, true>), grid, dim3(MG_NTHR), 0, st, (const T*)x, (const T*)nullptr, (const T*)nullptr, (const T*)nullptr,
                            (const float*)nullptr, (const float*)nullptr, (T*)nullptr, (float*)partial, P, C, sg.tpr, sg.rpb, sg.chunk, 0, 0.f, shift, 0, 0);
     MG_CHECK_LAUNCH("channel statistics (stage 1)");
     hipLaunchKernelGGL((stats_stage2<T, FIN>), dim3((C + 15) / 16, G), dim3(256), 0, st, (const float*)partial, (const T*)x, P, sums, sg.nchunks, C, shift,
@@ -681,20 +674,17 @@ int run_reduce(const void* x, const void* dh, const void* h, const void* g1, con
     dim3 grid(sg.nchunks, G);
     if (mg_opt(MG_OPT_NORM_BWD_VEC) && vec_geom_ok<T>(C) && act != MG_ACT_TANH) {
         // (d[gamma|beta] rows are 32-channel blocks; a thread's VEC channels start at a multiple of VEC and stay inside one block)
-        const float neg = act == MG_ACT_NONE ? 1.f : (act == MG_ACT_RELU ? 0.f : slope);
-        const bool hh = h != nullptr && act != MG_ACT_NONE;
-#define MG_BWD1(HASH, UPF) hipLaunchKernelGGL((bwd_stage1_vec<T, 2, HASH, UPF>), grid, dim3(NTHR), 0, st, (const T*)x, (const T*)dh, (const T*)h, \
-                           (const T*)g1, mean, rstd, (T*)dgb, (float*)partial, P, C, sg.chunk, neg, H, W)
-        if (hh) { if (up) MG_BWD1(true, true); else MG_BWD1(true, false); }
-        else    { if (up) MG_BWD1(false, true); else MG_BWD1(false, false); }
-#undef MG_BWD1
+        const float neg = mg_neg_slope(act, slope);
+        by_bool(h != nullptr && act != MG_ACT_NONE, [&](auto hh) { by_bool(up != 0, [&](auto upf) {
+            hipLaunchKernelGGL((bwd_stage1_vec<T, 2, hh.value, upf.value>), grid, dim3(MG_NTHR), 0, st, (const T*)x, (const T*)dh, (const T*)h,
+                               (const T*)g1, mean, rstd, (T*)dgb, (float*)partial, P, C, sg.chunk, neg, H, W); }); });
     }
     else if (h == nullptr)
-        hipLaunchKernelGGL((reduce_stage1<T, 1, false>), grid, dim3(NTHR), 0, st,
+        hipLaunchKernelGGL((reduce_stage1<T, 1, false>), grid, dim3(MG_NTHR), 0, st,
                            (const T*)x, (const T*)dh, (const T*)h, (const T*)g1, mean, rstd, (T*)dgb,
                            (float*)partial, P, C, sg.tpr, sg.rpb, sg.chunk, act, slope, up, H, W);
     else
-        hipLaunchKernelGGL((reduce_stage1<T, 1, true>), grid, dim3(NTHR), 0, st,
+        hipLaunchKernelGGL((reduce_stage1<T, 1, true>), grid, dim3(MG_NTHR), 0, st,
                            (const T*)x, (const T*)dh, (const T*)h, (const T*)g1, mean, rstd, (T*)dgb,
                            (float*)partial, P, C, sg.tpr, sg.rpb, sg.chunk, act, slope, up, H, W);
     MG_CHECK_LAUNCH("reduce_stage1");
@@ -723,9 +713,8 @@ extern "C" int mg_channel_stats(const void* x, int32_t dtype, int32_t G, int64_t
     MG_CHECK_NORM_GEOM("mg_channel_stats");
     MG_CHECK_ARG(x && sums && partial, "mg_channel_stats: null pointer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MG_BF16)
-        return run_stats<uint16_t, false>(x, G, P, C, shift != 0, sums, partial, 1.0, 1.0, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, st);
-    return run_stats<float, false>(x, G, P, C, shift != 0, sums, partial, 1.0, 1.0, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, st);
+    return mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        return run_stats<T, false>(x, G, P, C, shift != 0, sums, partial, 1.0, 1.0, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, st); });
 }
 
 extern "C" int mg_channel_stats_finalize(const void* x, int32_t dtype, int32_t G, int64_t P, int32_t C, float sum_scale, double count,
@@ -738,9 +727,8 @@ extern "C" int mg_channel_stats_finalize(const void* x, int32_t dtype, int32_t G
     MG_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr) && (running_mean == nullptr || G == 1),
                  "mg_channel_stats_finalize: running statistics need both buffers and G == 1");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MG_BF16)
-        return run_stats<uint16_t, true>(x, G, P, C, 1, sums, partial, (double)sum_scale, count, eps, momentum, running_mean, running_var, mean, rstd, st);
-    return run_stats<float, true>(x, G, P, C, 1, sums, partial, (double)sum_scale, count, eps, momentum, running_mean, running_var, mean, rstd, st);
+    return mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        return run_stats<T, true>(x, G, P, C, 1, sums, partial, (double)sum_scale, count, eps, momentum, running_mean, running_var, mean, rstd, st); });
 }
 
 extern "C" int mg_norm_act_fwd(const void* x, void* y, int32_t dtype, int32_t G, int64_t P, int32_t C,
@@ -750,27 +738,15 @@ extern "C" int mg_norm_act_fwd(const void* x, void* y, int32_t dtype, int32_t G,
     MG_CHECK_ARG(x && y && mean && rstd, "mg_norm_act_fwd: null pointer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t nq = (int64_t)G * P * (C / 4);
-    if (act != MG_ACT_TANH && (dtype == MG_BF16 ? vec_geom_ok<uint16_t>(C) : vec_geom_ok<float>(C))) {
-        const float neg = act == MG_ACT_NONE ? 1.f : (act == MG_ACT_RELU ? 0.f : slope);
-        const bool relu = act == MG_ACT_RELU;
-        if (dtype == MG_BF16) {
-            const int rows = NTHR / (C / 8);
-            hipLaunchKernelGGL((norm_act_fwd_vec<uint16_t, 4>), dim3(pix_grid(P, rows, 4, G), G), dim3(NTHR), 0, st,
-                               (const uint16_t*)x, (uint16_t*)y, P, C, mean, rstd, neg, relu, (const uint16_t*)resid);
-        } else {
-            const int rows = NTHR / (C / 4);
-            hipLaunchKernelGGL((norm_act_fwd_vec<float, 4>), dim3(pix_grid(P, rows, 4, G), G), dim3(NTHR), 0, st,
-                               (const float*)x, (float*)y, P, C, mean, rstd, neg, relu, (const float*)resid);
-        }
-        MG_CHECK_LAUNCH("mg_norm_act_fwd");
-        return MG_OK;
-    }
-    if (dtype == MG_BF16)
-        hipLaunchKernelGGL(norm_act_fwd_kernel<uint16_t>, dim3(ew_grid(nq)), dim3(NTHR), 0, st,
-                           (const uint16_t*)x, (uint16_t*)y, nq, P, C, mean, rstd, act, slope, (const uint16_t*)resid);
-    else
-        hipLaunchKernelGGL(norm_act_fwd_kernel<float>, dim3(ew_grid(nq)), dim3(NTHR), 0, st,
-                           (const float*)x, (float*)y, nq, P, C, mean, rstd, act, slope, (const float*)resid);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        if (act != MG_ACT_TANH && vec_geom_ok<T>(C)) {
+            const int rows = MG_NTHR / (C / VT<T>::VEC);
+            hipLaunchKernelGGL((norm_act_fwd_vec<T, 4>), dim3(pix_grid(P, rows, 4, G), G), dim3(MG_NTHR), 0, st,
+                               (const T*)x, (T*)y, P, C, mean, rstd, mg_neg_slope(act, slope), act == MG_ACT_RELU, (const T*)resid);
+        } else
+            hipLaunchKernelGGL(norm_act_fwd_kernel<T>, dim3(mg_ew_grid(nq, 8192)), dim3(MG_NTHR), 0, st,
+                               (const T*)x, (T*)y, nq, P, C, mean, rstd, act, slope, (const T*)resid);
+    });
     MG_CHECK_LAUNCH("mg_norm_act_fwd");
     return MG_OK;
 }
@@ -784,9 +760,8 @@ extern "C" int mg_norm_bwd_reduce(const void* dh, const void* h, const void* x, 
     MG_CHECK_ARG(dh && (h || act == MG_ACT_NONE) && x && mean && rstd && sums && partial, "mg_norm_bwd_reduce: null pointer");
     MG_CHECK_ARG(dgb == nullptr || G == 1, "mg_norm_bwd_reduce: dgb output requires G == 1");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MG_BF16)
-        return run_reduce<uint16_t>(x, dh, h, g1, mean, rstd, dgb, G, P, C, sums, partial, act, slope, st);
-    return run_reduce<float>(x, dh, h, g1, mean, rstd, dgb, G, P, C, sums, partial, act, slope, st);
+    return mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        return run_reduce<T>(x, dh, h, g1, mean, rstd, dgb, G, P, C, sums, partial, act, slope, st); });
 }
 
 extern "C" int mg_norm_bwd_reduce_up(const void* dh, const void* h, const void* x, const void* g1,
@@ -799,28 +774,21 @@ extern "C" int mg_norm_bwd_reduce_up(const void* dh, const void* h, const void* 
     MG_CHECK_ARG(dh && (h || act == MG_ACT_NONE) && x && mean && rstd && sums && partial, "mg_norm_bwd_reduce_up: null pointer");
     MG_CHECK_ARG(N > 0 && H > 0 && W > 0 && (H % 2) == 0 && (W % 2) == 0 && P < (1L << 31), "mg_norm_bwd_reduce_up: H, W must be even");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MG_BF16)
-        return run_reduce<uint16_t>(x, dh, h, g1, mean, rstd, dgb, G, P, C, sums, partial, act, slope, st, 1, H, W);
-    return run_reduce<float>(x, dh, h, g1, mean, rstd, dgb, G, P, C, sums, partial, act, slope, st, 1, H, W);
+    return mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        return run_reduce<T>(x, dh, h, g1, mean, rstd, dgb, G, P, C, sums, partial, act, slope, st, 1, H, W); });
 }
 
 template <typename T>
 static int launch_apply2(const mg_norm_apply2_desc& d, hipStream_t st)
 {
     constexpr int VEC = VT<T>::VEC;
-    const int rows = NTHR / (d.C / VEC);
+    const int rows = MG_NTHR / (d.C / VEC);
     const bool two = d.dh[1] != nullptr;
     const int64_t pout = d.up ? d.P / 4 : d.P;
-    auto neg = [](int act, float slope) { return act == MG_ACT_NONE ? 1.f : (act == MG_ACT_RELU ? 0.f : slope); };
-    const float n0 = neg(d.act[0], d.slope[0]), n1 = neg(d.act[1], d.slope[1]);
-    const dim3 grid(pix_grid(pout, rows, 1, 1)), blk(NTHR);
-    if (d.up) {
-        if (two) hipLaunchKernelGGL((norm_bwd_apply2_vec<T, 2, true>), grid, blk, 0, st, d, n0, n1);
-        else     hipLaunchKernelGGL((norm_bwd_apply2_vec<T, 1, true>), grid, blk, 0, st, d, n0, n1);
-    } else {
-        if (two) hipLaunchKernelGGL((norm_bwd_apply2_vec<T, 2, false>), grid, blk, 0, st, d, n0, n1);
-        else     hipLaunchKernelGGL((norm_bwd_apply2_vec<T, 1, false>), grid, blk, 0, st, d, n0, n1);
-    }
+    const float n0 = mg_neg_slope(d.act[0], d.slope[0]), n1 = mg_neg_slope(d.act[1], d.slope[1]);
+    const dim3 grid(pix_grid(pout, rows, 1, 1)), blk(MG_NTHR);
+    by_bool(d.up != 0, [&](auto up) { by_bool(two, [&](auto nb2) {
+        hipLaunchKernelGGL((norm_bwd_apply2_vec<T, nb2.value ? 2 : 1, up.value>), grid, blk, 0, st, d, n0, n1); }); });
     return 0;
 }
 
@@ -841,7 +809,7 @@ extern "C" int mg_norm_bwd_apply2(const mg_norm_apply2_desc* d, void* stream)
     MG_CHECK_ARG(!d->up || (d->H > 0 && d->W > 0 && (d->H % 2) == 0 && (d->W % 2) == 0 && d->P % ((int64_t)d->H * d->W) == 0),
                  "mg_norm_bwd_apply2: up needs even H, W and P = N*H*W");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d->dtype == MG_BF16) launch_apply2<uint16_t>(*d, st); else launch_apply2<float>(*d, st);
+    mg_by_dtype(d->dtype, [&](auto t) { launch_apply2<typename decltype(t)::type>(*d, st); });
     MG_CHECK_LAUNCH("mg_norm_bwd_apply2");
     return MG_OK;
 }
@@ -857,30 +825,17 @@ extern "C" int mg_norm_bwd_apply(const void* dh, const void* h, const void* x, c
     MG_CHECK_ARG(dh && (h || act == MG_ACT_NONE) && x && mean && rstd && s1 && s2 && dx, "mg_norm_bwd_apply: null pointer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t nq = (int64_t)G * P * (C / 4);
-    if (act != MG_ACT_TANH && (dtype == MG_BF16 ? vec_geom_ok<uint16_t>(C) : vec_geom_ok<float>(C))) {
-        const float neg = act == MG_ACT_NONE ? 1.f : (act == MG_ACT_RELU ? 0.f : slope);
-        if (dtype == MG_BF16) {
-            const int rows = NTHR / (C / 8);
-            hipLaunchKernelGGL((norm_bwd_apply_vec<uint16_t, 2>), dim3(pix_grid(P, rows, 2, G), G), dim3(NTHR), 0, st,
-                               (const uint16_t*)dh, (const uint16_t*)h, (const uint16_t*)x, (const uint16_t*)g1, (uint16_t*)dx,
-                               P, C, mean, rstd, s1, s2, sgs, sscale, neg);
-        } else {
-            const int rows = NTHR / (C / 4);
-            hipLaunchKernelGGL((norm_bwd_apply_vec<float, 2>), dim3(pix_grid(P, rows, 2, G), G), dim3(NTHR), 0, st,
-                               (const float*)dh, (const float*)h, (const float*)x, (const float*)g1, (float*)dx,
-                               P, C, mean, rstd, s1, s2, sgs, sscale, neg);
-        }
-        MG_CHECK_LAUNCH("mg_norm_bwd_apply");
-        return MG_OK;
-    }
-    if (dtype == MG_BF16)
-        hipLaunchKernelGGL(norm_bwd_apply_kernel<uint16_t>, dim3(ew_grid(nq)), dim3(NTHR), 0, st,
-                           (const uint16_t*)dh, (const uint16_t*)h, (const uint16_t*)x, (const uint16_t*)g1, (uint16_t*)dx,
-                           nq, P, C, mean, rstd, s1, s2, sgs, sscale, act, slope);
-    else
-        hipLaunchKernelGGL(norm_bwd_apply_kernel<float>, dim3(ew_grid(nq)), dim3(NTHR), 0, st,
-                           (const float*)dh, (const float*)h, (const float*)x, (const float*)g1, (float*)dx,
-                           nq, P, C, mean, rstd, s1, s2, sgs, sscale, act, slope);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        if (act != MG_ACT_TANH && vec_geom_ok<T>(C)) {
+            const int rows = MG_NTHR / (C / VT<T>::VEC);
+            hipLaunchKernelGGL((norm_bwd_apply_vec<T, 2>), dim3(pix_grid(P, rows, 2, G), G), dim3(MG_NTHR), 0, st,
+                               (const T*)dh, (const T*)h, (const T*)x, (const T*)g1, (T*)dx,
+                               P, C, mean, rstd, s1, s2, sgs, sscale, mg_neg_slope(act, slope));
+        } else
+            hipLaunchKernelGGL(norm_bwd_apply_kernel<T>, dim3(mg_ew_grid(nq, 8192)), dim3(MG_NTHR), 0, st,
+                               (const T*)dh, (const T*)h, (const T*)x, (const T*)g1, (T*)dx,
+                               nq, P, C, mean, rstd, s1, s2, sgs, sscale, act, slope);
+    });
     MG_CHECK_LAUNCH("mg_norm_bwd_apply");
     return MG_OK;
 }

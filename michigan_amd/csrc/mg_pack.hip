@@ -4,11 +4,9 @@
 // Row map (GEMM row of output channel co): plain conv  -> co
 //                                         fused SPADE -> 64*(co/32) + co%32 (+32 for the beta tensor)
 #include "mg_common.h"
+#include "mg_launch.h"
 
 namespace {
-
-constexpr int NTHR = 256;
-static inline int ew_grid(int64_t n) { int64_t b = (n + NTHR - 1) / NTHR; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 
 // GEMM row r -> (source tensor, channel) ; returns -1 for a padding row
 __device__ __forceinline__ int row_to_co(int r, int cout, bool two, int& which)
@@ -72,8 +70,8 @@ extern "C" int mg_pack_weight(const float* w0, const float* w1, void* dst, int32
                  "mg_pack_weight: destination too small");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)taps * rows_p * cols_p;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(pack_kernel<uint16_t>, dim3(ew_grid(total)), dim3(NTHR), 0, st, w0, w1, (uint16_t*)dst, cout, cin, taps, rows_p, cols_p, mode);
-    else hipLaunchKernelGGL(pack_kernel<float>, dim3(ew_grid(total)), dim3(NTHR), 0, st, w0, w1, (float*)dst, cout, cin, taps, rows_p, cols_p, mode);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pack_kernel<T>, dim3(mg_ew_grid(total, 4096)), dim3(MG_NTHR), 0, st, w0, w1, (T*)dst, cout, cin, taps, rows_p, cols_p, mode); });
     MG_CHECK_LAUNCH("mg_pack_weight");
     return MG_OK;
 }
@@ -86,7 +84,7 @@ extern "C" int mg_unpack_wgrad(const float* dw, float* d0, float* d1, int32_t co
     MG_CHECK_ARG(rows >= (d1 ? 2 * ((cout + 31) / 32) * 32 : cout), "mg_unpack_wgrad: source has too few rows");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)(d1 ? 2 : 1) * cout * cin * taps;
-    hipLaunchKernelGGL(unpack_kernel, dim3(ew_grid(total)), dim3(NTHR), 0, st, dw, d0, d1, cout, cin, taps, rows, cols);
+    hipLaunchKernelGGL(unpack_kernel, dim3(mg_ew_grid(total, 4096)), dim3(MG_NTHR), 0, st, dw, d0, d1, cout, cin, taps, rows, cols);
     MG_CHECK_LAUNCH("mg_unpack_wgrad");
     return MG_OK;
 }

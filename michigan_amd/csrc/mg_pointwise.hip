@@ -4,20 +4,15 @@
 // hardware fragment-layout probes used by the test-suite.
 // One thread = one quad (4 consecutive channels) -> 8 B (bf16) / 16 B (f32) accesses.
 #include "mg_common.h"
+#include "mg_launch.h"
 
 namespace {
-
-constexpr int NTHR = 256;
-static inline int ew_grid(int64_t n) { int64_t b = (n + NTHR - 1) / NTHR; return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
-
-#define GRID_STRIDE(i, n) \
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 template <typename T>
 __global__ void act_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y, T* __restrict__ dpre,
                                int64_t nquads, int act, float slope)
 {
-    GRID_STRIDE(i, nquads) {
+    MG_GRID_STRIDE(i, nquads) {
         const f32x4_t d = ET<T>::load4(dy + i * 4), v = ET<T>::load4(y + i * 4);
         f32x4_t o;
 #pragma unroll
@@ -32,7 +27,7 @@ __global__ void up2_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int N
 {
     const int c4 = C / 4; const int Ho = 2 * H, Wo = 2 * W;
     const int64_t n = (int64_t)N * Ho * Wo * c4;
-    GRID_STRIDE(i, n) {
+    MG_GRID_STRIDE(i, n) {
         const int qd = (int)(i % c4); int64_t p = i / c4;
         const int ox = (int)(p % Wo); p /= Wo;
         const int oy = (int)(p % Ho); const int b = (int)(p / Ho);
@@ -47,7 +42,7 @@ __global__ void reflect_pad_fwd_kernel(const T* __restrict__ x, T* __restrict__ 
 {
     const int c4 = C / 4; const int Ho = H + 2 * P, Wo = W + 2 * P;
     const int64_t n = (int64_t)N * Ho * Wo * c4;
-    GRID_STRIDE(i, n) {
+    MG_GRID_STRIDE(i, n) {
         const int qd = (int)(i % c4); int64_t p = i / c4;
         const int ox = (int)(p % Wo); p /= Wo;
         const int oy = (int)(p % Ho); const int b = (int)(p / Ho);
@@ -62,7 +57,7 @@ __global__ void reflect_pad_bwd_kernel(const T* __restrict__ dy, T* __restrict__
 {
     const int c4 = C / 4; const int Ho = H + 2 * P, Wo = W + 2 * P;
     const int64_t n = (int64_t)N * H * W * c4;
-    GRID_STRIDE(i, n) {
+    MG_GRID_STRIDE(i, n) {
         const int qd = (int)(i % c4); int64_t p = i / c4;
         const int ix = (int)(p % W); p /= W;
         const int iy = (int)(p % H); const int b = (int)(p / H);
@@ -89,7 +84,7 @@ __global__ void up2_bwd_kernel(const T* __restrict__ dy, T* __restrict__ dx, int
 {
     const int c4 = C / 4; const int Wo = 2 * W;
     const int64_t n = (int64_t)N * H * W * c4;
-    GRID_STRIDE(i, n) {
+    MG_GRID_STRIDE(i, n) {
         const int qd = (int)(i % c4); int64_t p = i / c4;
         const int ix = (int)(p % W); p /= W;
         const int iy = (int)(p % H); const int b = (int)(p / H);
@@ -112,7 +107,7 @@ __global__ void avgpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, i
 {
     const int c4 = C / 4;
     const int64_t n = (int64_t)N * Ho * Wo * c4;
-    GRID_STRIDE(i, n) {
+    MG_GRID_STRIDE(i, n) {
         const int qd = (int)(i % c4); int64_t p = i / c4;
         const int ox = (int)(p % Wo); p /= Wo;
         const int oy = (int)(p % Ho); const int b = (int)(p / Ho);
@@ -137,7 +132,7 @@ __global__ void avgpool_bwd_kernel(const T* __restrict__ dy, T* __restrict__ dx,
 {
     const int c4 = C / 4;
     const int64_t n = (int64_t)N * H * W * c4;
-    GRID_STRIDE(i, n) {
+    MG_GRID_STRIDE(i, n) {
         const int qd = (int)(i % c4); int64_t p = i / c4;
         const int ix = (int)(p % W); p /= W;
         const int iy = (int)(p % H); const int b = (int)(p / H);
@@ -162,7 +157,7 @@ __global__ void maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, i
 {
     const int c4 = C / 4;
     const int64_t n = (int64_t)N * Ho * Wo * c4;
-    GRID_STRIDE(i, n) {
+    MG_GRID_STRIDE(i, n) {
         const int qd = (int)(i % c4); int64_t p = i / c4;
         const int ox = (int)(p % Wo); p /= Wo;
         const int oy = (int)(p % Ho); const int b = (int)(p / Ho);
@@ -181,7 +176,7 @@ __global__ void maxpool_bwd_kernel(const T* __restrict__ dy, const T* __restrict
 {
     const int c4 = C / 4;
     const int64_t n = (int64_t)N * H * W * c4;
-    GRID_STRIDE(i, n) {
+    MG_GRID_STRIDE(i, n) {
         const int qd = (int)(i % c4); int64_t p = i / c4;
         const int ix = (int)(p % W); p /= W;
         const int iy = (int)(p % H); const int b = (int)(p / H);
@@ -211,7 +206,7 @@ __global__ void blend_fwd_kernel(const T* __restrict__ bg, const T* __restrict__
                                  const float* __restrict__ back, T* __restrict__ y, int64_t nquads, int C, int act, float slope)
 {
     const int c4 = C / 4;
-    GRID_STRIDE(i, nquads) {
+    MG_GRID_STRIDE(i, nquads) {
         const int64_t p = i / c4;
         const float wb = 1.f - hair[p], wx = 1.f - back[p];
         const f32x4_t b = ET<T>::load4(bg + i * 4), v = ET<T>::load4(x + i * 4);
@@ -227,7 +222,7 @@ __global__ void blend_bwd_kernel(const T* __restrict__ dy, const T* __restrict__
                                  int act, float slope)
 {
     const int c4 = C / 4;
-    GRID_STRIDE(i, nquads) {
+    MG_GRID_STRIDE(i, nquads) {
         const int64_t p = i / c4;
         const float wb = 1.f - hair[p], wx = 1.f - back[p];
         f32x4_t d = ET<T>::load4(dy + i * 4);
@@ -248,7 +243,7 @@ __global__ void blend_bwd_kernel(const T* __restrict__ dy, const T* __restrict__
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             int64_t n, float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt, float gscale)
 {
-    GRID_STRIDE(i, n) {
+    MG_GRID_STRIDE(i, n) {
         const float gi = g[i] * gscale;
         // exp_avg.lerp_(grad, 1 - beta1) with torch's two-branch lerp (ATen Lerp.h): weight >= 0.5 evaluates end - (end - start) * (1 - weight).
         // beta1 = 0 (the reference's TTUR setting, pix2pix_model.py:137-145) must give m = g EXACTLY: the one-branch form m + (g - m) rounds
@@ -268,12 +263,12 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 // backward: da = sign(a - b) * (*gscale) / numel in the activation dtype, ONE pass.  The eager form
 // (float casts, sub, abs, mean and their autograd) is ~10 passes over each feature map.
 template <typename T>
-__global__ __launch_bounds__(NTHR) void l1_partial_kernel(const T* __restrict__ a, const T* __restrict__ b,
+__global__ __launch_bounds__(MG_NTHR) void l1_partial_kernel(const T* __restrict__ a, const T* __restrict__ b,
                                                           float* __restrict__ partial, int64_t nquads)
 {
-    __shared__ float red[NTHR / 64];
+    __shared__ float red[MG_NTHR / 64];
     float s = 0.f;
-    GRID_STRIDE(i, nquads) {
+    MG_GRID_STRIDE(i, nquads) {
         const f32x4_t x = ET<T>::load4(a + i * 4), y = ET<T>::load4(b + i * 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) s += fabsf(x[j] - y[j]);
@@ -282,7 +277,7 @@ __global__ __launch_bounds__(NTHR) void l1_partial_kernel(const T* __restrict__ 
     for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) { float t = 0.f; for (int w = 0; w < NTHR / 64; ++w) t += red[w]; partial[blockIdx.x] = t; }
+    if (threadIdx.x == 0) { float t = 0.f; for (int w = 0; w < MG_NTHR / 64; ++w) t += red[w]; partial[blockIdx.x] = t; }
 }
 __global__ void l1_final_kernel(const float* __restrict__ partial, int n, double inv_numel, float* __restrict__ out)
 {
@@ -299,7 +294,7 @@ __global__ void l1_bwd_kernel(const T* __restrict__ a, const T* __restrict__ b, 
                               float inv_numel, T* __restrict__ da, int64_t nquads)
 {
     const float g = gscale[0] * inv_numel;
-    GRID_STRIDE(i, nquads) {
+    MG_GRID_STRIDE(i, nquads) {
         const f32x4_t x = ET<T>::load4(a + i * 4), y = ET<T>::load4(b + i * 4);
         f32x4_t o;
 #pragma unroll
@@ -349,11 +344,6 @@ __global__ void probe_tr16_kernel(const uint16_t* in, uint16_t* out)
 #define MG_EW_GEOM(name) \
     MG_CHECK_ARG(dtype == MG_F32 || dtype == MG_BF16, name ": bad dtype %d", dtype); \
     MG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && (C % 4) == 0, name ": bad geometry N=%d H=%d W=%d C=%d (C %% 4 == 0)", N, H, W, C)
-#define MG_LAUNCH2(kern, grid, ...) do { \
-    if (dtype == MG_BF16) hipLaunchKernelGGL(kern<uint16_t>, dim3(grid), dim3(NTHR), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL(kern<float>, dim3(grid), dim3(NTHR), 0, st, __VA_ARGS__); } while (0)
-
-#define CT(p) reinterpret_cast<const T_*>(p)
 
 extern "C" int mg_act_bwd(const void* dy, const void* y, void* dpre, int32_t dtype, int64_t numel,
                           int32_t act, float slope, void* stream)
@@ -363,8 +353,8 @@ extern "C" int mg_act_bwd(const void* dy, const void* y, void* dpre, int32_t dty
     MG_CHECK_ARG(numel > 0 && (numel % 4) == 0, "mg_act_bwd: numel=%ld must be a positive multiple of 4", (long)numel);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t nq = numel / 4;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(act_bwd_kernel<uint16_t>, dim3(ew_grid(nq)), dim3(NTHR), 0, st, (const uint16_t*)dy, (const uint16_t*)y, (uint16_t*)dpre, nq, act, slope);
-    else hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(ew_grid(nq)), dim3(NTHR), 0, st, (const float*)dy, (const float*)y, (float*)dpre, nq, act, slope);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(act_bwd_kernel<T>, dim3(mg_ew_grid(nq, 8192)), dim3(MG_NTHR), 0, st, (const T*)dy, (const T*)y, (T*)dpre, nq, act, slope); });
     MG_CHECK_LAUNCH("mg_act_bwd");
     return MG_OK;
 }
@@ -373,9 +363,9 @@ extern "C" int mg_upsample2x_fwd(const void* x, void* y, int32_t dtype, int32_t 
 {
     MG_EW_GEOM("mg_upsample2x_fwd"); MG_CHECK_ARG(x && y, "mg_upsample2x_fwd: null pointer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int g = ew_grid((int64_t)N * 4 * H * W * (C / 4));
-    if (dtype == MG_BF16) hipLaunchKernelGGL(up2_fwd_kernel<uint16_t>, dim3(g), dim3(NTHR), 0, st, (const uint16_t*)x, (uint16_t*)y, N, H, W, C);
-    else hipLaunchKernelGGL(up2_fwd_kernel<float>, dim3(g), dim3(NTHR), 0, st, (const float*)x, (float*)y, N, H, W, C);
+    const int g = mg_ew_grid((int64_t)N * 4 * H * W * (C / 4), 8192);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(up2_fwd_kernel<T>, dim3(g), dim3(MG_NTHR), 0, st, (const T*)x, (T*)y, N, H, W, C); });
     MG_CHECK_LAUNCH("mg_upsample2x_fwd");
     return MG_OK;
 }
@@ -383,9 +373,9 @@ extern "C" int mg_upsample2x_bwd(const void* dy, void* dx, int32_t dtype, int32_
 {
     MG_EW_GEOM("mg_upsample2x_bwd"); MG_CHECK_ARG(dy && dx, "mg_upsample2x_bwd: null pointer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int g = ew_grid((int64_t)N * H * W * (C / 4));
-    if (dtype == MG_BF16) hipLaunchKernelGGL(up2_bwd_kernel<uint16_t>, dim3(g), dim3(NTHR), 0, st, (const uint16_t*)dy, (uint16_t*)dx, N, H, W, C);
-    else hipLaunchKernelGGL(up2_bwd_kernel<float>, dim3(g), dim3(NTHR), 0, st, (const float*)dy, (float*)dx, N, H, W, C);
+    const int g = mg_ew_grid((int64_t)N * H * W * (C / 4), 8192);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(up2_bwd_kernel<T>, dim3(g), dim3(MG_NTHR), 0, st, (const T*)dy, (T*)dx, N, H, W, C); });
     MG_CHECK_LAUNCH("mg_upsample2x_bwd");
     return MG_OK;
 }
@@ -395,9 +385,9 @@ extern "C" int mg_reflect_pad_fwd(const void* x, void* y, int32_t dtype, int32_t
     MG_EW_GEOM("mg_reflect_pad_fwd"); MG_CHECK_ARG(x && y, "mg_reflect_pad_fwd: null pointer");
     MG_CHECK_ARG(P >= 1 && P < H && P < W, "mg_reflect_pad_fwd: pad %d must be in [1, min(H, W))", P);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int g = ew_grid((int64_t)N * (H + 2 * P) * (W + 2 * P) * (C / 4));
-    if (dtype == MG_BF16) hipLaunchKernelGGL(reflect_pad_fwd_kernel<uint16_t>, dim3(g), dim3(NTHR), 0, st, (const uint16_t*)x, (uint16_t*)y, N, H, W, C, P);
-    else hipLaunchKernelGGL(reflect_pad_fwd_kernel<float>, dim3(g), dim3(NTHR), 0, st, (const float*)x, (float*)y, N, H, W, C, P);
+    const int g = mg_ew_grid((int64_t)N * (H + 2 * P) * (W + 2 * P) * (C / 4), 8192);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(reflect_pad_fwd_kernel<T>, dim3(g), dim3(MG_NTHR), 0, st, (const T*)x, (T*)y, N, H, W, C, P); });
     MG_CHECK_LAUNCH("mg_reflect_pad_fwd");
     return MG_OK;
 }
@@ -406,9 +396,9 @@ extern "C" int mg_reflect_pad_bwd(const void* dy, void* dx, int32_t dtype, int32
     MG_EW_GEOM("mg_reflect_pad_bwd"); MG_CHECK_ARG(dy && dx, "mg_reflect_pad_bwd: null pointer");
     MG_CHECK_ARG(P >= 1 && P < H && P < W, "mg_reflect_pad_bwd: pad %d must be in [1, min(H, W))", P);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int g = ew_grid((int64_t)N * H * W * (C / 4));
-    if (dtype == MG_BF16) hipLaunchKernelGGL(reflect_pad_bwd_kernel<uint16_t>, dim3(g), dim3(NTHR), 0, st, (const uint16_t*)dy, (uint16_t*)dx, N, H, W, C, P);
-    else hipLaunchKernelGGL(reflect_pad_bwd_kernel<float>, dim3(g), dim3(NTHR), 0, st, (const float*)dy, (float*)dx, N, H, W, C, P);
+    const int g = mg_ew_grid((int64_t)N * H * W * (C / 4), 8192);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(reflect_pad_bwd_kernel<T>, dim3(g), dim3(MG_NTHR), 0, st, (const T*)dy, (T*)dx, N, H, W, C, P); });
     MG_CHECK_LAUNCH("mg_reflect_pad_bwd");
     return MG_OK;
 }
@@ -418,9 +408,9 @@ extern "C" int mg_avgpool3s2_fwd(const void* x, void* y, int32_t dtype, int32_t 
     MG_EW_GEOM("mg_avgpool3s2_fwd"); MG_CHECK_ARG(x && y, "mg_avgpool3s2_fwd: null pointer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int g = ew_grid((int64_t)N * Ho * Wo * (C / 4));
-    if (dtype == MG_BF16) hipLaunchKernelGGL(avgpool_fwd_kernel<uint16_t>, dim3(g), dim3(NTHR), 0, st, (const uint16_t*)x, (uint16_t*)y, N, H, W, C, Ho, Wo);
-    else hipLaunchKernelGGL(avgpool_fwd_kernel<float>, dim3(g), dim3(NTHR), 0, st, (const float*)x, (float*)y, N, H, W, C, Ho, Wo);
+    const int g = mg_ew_grid((int64_t)N * Ho * Wo * (C / 4), 8192);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(avgpool_fwd_kernel<T>, dim3(g), dim3(MG_NTHR), 0, st, (const T*)x, (T*)y, N, H, W, C, Ho, Wo); });
     MG_CHECK_LAUNCH("mg_avgpool3s2_fwd");
     return MG_OK;
 }
@@ -429,9 +419,9 @@ extern "C" int mg_avgpool3s2_bwd(const void* dy, void* dx, int32_t dtype, int32_
     MG_EW_GEOM("mg_avgpool3s2_bwd"); MG_CHECK_ARG(dy && dx, "mg_avgpool3s2_bwd: null pointer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int g = ew_grid((int64_t)N * H * W * (C / 4));
-    if (dtype == MG_BF16) hipLaunchKernelGGL(avgpool_bwd_kernel<uint16_t>, dim3(g), dim3(NTHR), 0, st, (const uint16_t*)dy, (uint16_t*)dx, N, H, W, C, Ho, Wo);
-    else hipLaunchKernelGGL(avgpool_bwd_kernel<float>, dim3(g), dim3(NTHR), 0, st, (const float*)dy, (float*)dx, N, H, W, C, Ho, Wo);
+    const int g = mg_ew_grid((int64_t)N * H * W * (C / 4), 8192);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(avgpool_bwd_kernel<T>, dim3(g), dim3(MG_NTHR), 0, st, (const T*)dy, (T*)dx, N, H, W, C, Ho, Wo); });
     MG_CHECK_LAUNCH("mg_avgpool3s2_bwd");
     return MG_OK;
 }
@@ -442,9 +432,9 @@ extern "C" int mg_maxpool2_fwd(const void* x, void* y, int32_t dtype, int32_t N,
     MG_CHECK_ARG(H >= 2 && W >= 2, "mg_maxpool2_fwd: H, W must be >= 2");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int Ho = H / 2, Wo = W / 2;
-    const int g = ew_grid((int64_t)N * Ho * Wo * (C / 4));
-    if (dtype == MG_BF16) hipLaunchKernelGGL(maxpool_fwd_kernel<uint16_t>, dim3(g), dim3(NTHR), 0, st, (const uint16_t*)x, (uint16_t*)y, N, H, W, C, Ho, Wo);
-    else hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(g), dim3(NTHR), 0, st, (const float*)x, (float*)y, N, H, W, C, Ho, Wo);
+    const int g = mg_ew_grid((int64_t)N * Ho * Wo * (C / 4), 8192);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(g), dim3(MG_NTHR), 0, st, (const T*)x, (T*)y, N, H, W, C, Ho, Wo); });
     MG_CHECK_LAUNCH("mg_maxpool2_fwd");
     return MG_OK;
 }
@@ -455,7 +445,7 @@ template <typename T>
 __global__ void assemble_nhwc8_kernel(const float* __restrict__ planar, int cp, const T* __restrict__ nhwc, int cs, int cf,
                                       T* __restrict__ out, int64_t npix, int64_t hw)
 {
-    GRID_STRIDE(i, npix) {
+    MG_GRID_STRIDE(i, npix) {
         const int64_t n = i / hw, p = i - n * hw;
         float v[8];
 #pragma unroll
@@ -479,8 +469,8 @@ extern "C" int mg_assemble_nhwc8(const float* planar, int32_t cp, const void* nh
                  "mg_assemble_nhwc8: bad geometry (cp + cf <= 8, cf <= cs)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t npix = (int64_t)N * HW;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(assemble_nhwc8_kernel<uint16_t>, dim3(ew_grid(npix)), dim3(NTHR), 0, st, planar, cp, (const uint16_t*)nhwc, cs, cf, (uint16_t*)out, npix, HW);
-    else hipLaunchKernelGGL(assemble_nhwc8_kernel<float>, dim3(ew_grid(npix)), dim3(NTHR), 0, st, planar, cp, (const float*)nhwc, cs, cf, (float*)out, npix, HW);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(assemble_nhwc8_kernel<T>, dim3(mg_ew_grid(npix, 8192)), dim3(MG_NTHR), 0, st, planar, cp, (const T*)nhwc, cs, cf, (T*)out, npix, HW); });
     MG_CHECK_LAUNCH("mg_assemble_nhwc8");
     return MG_OK;
 }
@@ -492,7 +482,7 @@ template <typename T>
 __global__ void grad_sum_act_kernel(const T* __restrict__ g1, const T* __restrict__ g2, const T* __restrict__ y, T* __restrict__ out,
                                     int64_t nquads, int act, float slope)
 {
-    GRID_STRIDE(i, nquads) {
+    MG_GRID_STRIDE(i, nquads) {
         f32x4_t a = ET<T>::load4(g1 + i * 4);
         if (g2) { const f32x4_t b = ET<T>::load4(g2 + i * 4);
 #pragma unroll
@@ -511,8 +501,8 @@ extern "C" int mg_grad_sum_act(const void* g1, const void* g2, const void* y, vo
     MG_CHECK_ARG((dtype == MG_F32 || dtype == MG_BF16) && numel > 0 && (numel % 4) == 0, "mg_grad_sum_act: numel must be a positive multiple of 4");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t nq = numel / 4;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(grad_sum_act_kernel<uint16_t>, dim3(ew_grid(nq)), dim3(NTHR), 0, st, (const uint16_t*)g1, (const uint16_t*)g2, (const uint16_t*)y, (uint16_t*)out, nq, act, slope);
-    else hipLaunchKernelGGL(grad_sum_act_kernel<float>, dim3(ew_grid(nq)), dim3(NTHR), 0, st, (const float*)g1, (const float*)g2, (const float*)y, (float*)out, nq, act, slope);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(grad_sum_act_kernel<T>, dim3(mg_ew_grid(nq, 8192)), dim3(MG_NTHR), 0, st, (const T*)g1, (const T*)g2, (const T*)y, (T*)out, nq, act, slope); });
     MG_CHECK_LAUNCH("mg_grad_sum_act");
     return MG_OK;
 }
@@ -523,9 +513,9 @@ extern "C" int mg_maxpool2_bwd(const void* dy, const void* x, void* dx, int32_t 
     MG_CHECK_ARG(H >= 2 && W >= 2, "mg_maxpool2_bwd: H, W must be >= 2");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int Ho = H / 2, Wo = W / 2;
-    const int g = ew_grid((int64_t)N * H * W * (C / 4));
-    if (dtype == MG_BF16) hipLaunchKernelGGL(maxpool_bwd_kernel<uint16_t>, dim3(g), dim3(NTHR), 0, st, (const uint16_t*)dy, (const uint16_t*)x, (uint16_t*)dx, N, H, W, C, Ho, Wo, relu_input);
-    else hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(g), dim3(NTHR), 0, st, (const float*)dy, (const float*)x, (float*)dx, N, H, W, C, Ho, Wo, relu_input);
+    const int g = mg_ew_grid((int64_t)N * H * W * (C / 4), 8192);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(g), dim3(MG_NTHR), 0, st, (const T*)dy, (const T*)x, (T*)dx, N, H, W, C, Ho, Wo, relu_input); });
     MG_CHECK_LAUNCH("mg_maxpool2_bwd");
     return MG_OK;
 }
@@ -537,8 +527,8 @@ extern "C" int mg_blend_fwd(const void* bg, const void* x, const float* hair, co
     MG_CHECK_ARG((dtype == MG_F32 || dtype == MG_BF16) && P > 0 && C > 0 && (C % 4) == 0, "mg_blend_fwd: bad geometry");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t nq = P * (C / 4);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(blend_fwd_kernel<uint16_t>, dim3(ew_grid(nq)), dim3(NTHR), 0, st, (const uint16_t*)bg, (const uint16_t*)x, hair, back, (uint16_t*)y, nq, C, act, slope);
-    else hipLaunchKernelGGL(blend_fwd_kernel<float>, dim3(ew_grid(nq)), dim3(NTHR), 0, st, (const float*)bg, (const float*)x, hair, back, (float*)y, nq, C, act, slope);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(blend_fwd_kernel<T>, dim3(mg_ew_grid(nq, 8192)), dim3(MG_NTHR), 0, st, (const T*)bg, (const T*)x, hair, back, (T*)y, nq, C, act, slope); });
     MG_CHECK_LAUNCH("mg_blend_fwd");
     return MG_OK;
 }
@@ -549,8 +539,8 @@ extern "C" int mg_blend_bwd(const void* dy, const void* y, const float* hair, co
     MG_CHECK_ARG((dtype == MG_F32 || dtype == MG_BF16) && P > 0 && C > 0 && (C % 4) == 0, "mg_blend_bwd: bad geometry");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t nq = P * (C / 4);
-    if (dtype == MG_BF16) hipLaunchKernelGGL(blend_bwd_kernel<uint16_t>, dim3(ew_grid(nq)), dim3(NTHR), 0, st, (const uint16_t*)dy, (const uint16_t*)y, hair, back, (uint16_t*)dbg, (uint16_t*)dx, nq, C, act, slope);
-    else hipLaunchKernelGGL(blend_bwd_kernel<float>, dim3(ew_grid(nq)), dim3(NTHR), 0, st, (const float*)dy, (const float*)y, hair, back, (float*)dbg, (float*)dx, nq, C, act, slope);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(blend_bwd_kernel<T>, dim3(mg_ew_grid(nq, 8192)), dim3(MG_NTHR), 0, st, (const T*)dy, (const T*)y, hair, back, (T*)dbg, (T*)dx, nq, C, act, slope); });
     MG_CHECK_LAUNCH("mg_blend_bwd");
     return MG_OK;
 }
@@ -564,7 +554,7 @@ extern "C" int mg_adam_step(float* param, const float* grad, float* exp_avg, flo
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const double bc1 = 1.0 - pow((double)beta1, (double)step);
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(numel)), dim3(NTHR), 0, st, param, grad, exp_avg, exp_avg_sq, numel,
+    hipLaunchKernelGGL(adam_kernel, dim3(mg_ew_grid(numel, 8192)), dim3(MG_NTHR), 0, st, param, grad, exp_avg, exp_avg_sq, numel,
                        lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), grad_scale);
     MG_CHECK_LAUNCH("mg_adam_step");
     return MG_OK;
@@ -591,9 +581,9 @@ extern "C" int mg_l1_mean_fwd(const void* a, const void* b, int32_t dtype, int64
     MG_CHECK_ARG((dtype == MG_F32 || dtype == MG_BF16) && numel > 0 && (numel % 4) == 0, "mg_l1_mean_fwd: numel must be a positive multiple of 4");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t nq = numel / 4;
-    int grid = ew_grid(nq); if (grid > 1024) grid = 1024;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(l1_partial_kernel<uint16_t>, dim3(grid), dim3(NTHR), 0, st, (const uint16_t*)a, (const uint16_t*)b, partial, nq);
-    else hipLaunchKernelGGL(l1_partial_kernel<float>, dim3(grid), dim3(NTHR), 0, st, (const float*)a, (const float*)b, partial, nq);
+    int grid = mg_ew_grid(nq, 8192); if (grid > 1024) grid = 1024;
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(l1_partial_kernel<T>, dim3(grid), dim3(MG_NTHR), 0, st, (const T*)a, (const T*)b, partial, nq); });
     MG_CHECK_LAUNCH("mg_l1_mean_fwd");
     hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(256), 0, st, (const float*)partial, grid, 1.0 / (double)numel, out);
     MG_CHECK_LAUNCH("mg_l1_mean_fwd(final)");
@@ -605,8 +595,8 @@ extern "C" int mg_l1_mean_bwd(const void* a, const void* b, const float* gscale,
     MG_CHECK_ARG((dtype == MG_F32 || dtype == MG_BF16) && numel > 0 && (numel % 4) == 0, "mg_l1_mean_bwd: numel must be a positive multiple of 4");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t nq = numel / 4;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(l1_bwd_kernel<uint16_t>, dim3(ew_grid(nq)), dim3(NTHR), 0, st, (const uint16_t*)a, (const uint16_t*)b, gscale, (float)(1.0 / (double)numel), (uint16_t*)da, nq);
-    else hipLaunchKernelGGL(l1_bwd_kernel<float>, dim3(ew_grid(nq)), dim3(NTHR), 0, st, (const float*)a, (const float*)b, gscale, (float)(1.0 / (double)numel), (float*)da, nq);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(l1_bwd_kernel<T>, dim3(mg_ew_grid(nq, 8192)), dim3(MG_NTHR), 0, st, (const T*)a, (const T*)b, gscale, (float)(1.0 / (double)numel), (T*)da, nq); });
     MG_CHECK_LAUNCH("mg_l1_mean_bwd");
     return MG_OK;
 }
