@@ -6,6 +6,8 @@ Tolerances (stated per dtype):
          summation order differs from the float64 emulator)
   bf16 : |hip - ref| <= 2^-7 * max|ref|   (one bf16 ulp at the top of the range:
          both sides round an fp32/fp64 accumulation to bf16 once)
+That bound is one ulp of the LARGEST value; tests/test_gpu_exact_sums.py holds the bf16 kernels tighter -- bit equality with the
+once-rounded float64 value on operands whose sums are exact -- and is where "rounds once" itself is pinned.
 """
 import os
 
