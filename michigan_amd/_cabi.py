@@ -18,6 +18,7 @@ MG_EPI_PLAIN, MG_EPI_SPADE = 0, 1
 MG_MAX_TAPS = 64
 MG_ABI_VERSION = 9
 MG_COMM_ID_BYTES = 128
+MG_EXT_FEATURE_LOSSES = 1                  # include/michigan_hip/feature_losses.h: what mg_ext_version() returns
 
 # enum mg_option (include/michigan_hip.h): the tuning switches of mg_set_option / mg_get_option; OPT_PROBE_* exist in -DMG_PROBES=1 builds only
 OPT_CONV_BIGTILES, OPT_CONV_HALO, OPT_WGRAD3X3, OPT_CONV_HALO_BIG, OPT_CONV_SPLITK, OPT_CONV_THIN, OPT_CONV_WIDE, OPT_CONV_DOT = 1, 2, 3, 4, 5, 6, 7, 8
@@ -91,6 +92,13 @@ class SnLayer(ctypes.Structure):
     _fields_ = [("w", _vp), ("u", _vp), ("v", _vp), ("u_copy", _vp), ("v_copy", _vp), ("sigma", _vp),
                 ("t1", _vp), ("t2", _vp), ("partial", _vp),
                 ("rows", _i32), ("cols", _i32), ("first_block_k1", _i32), ("first_block_k3", _i32)]
+
+
+class FeatMomentDesc(ctypes.Structure):
+    """struct mg_feat_moment_desc (include/michigan_hip/feature_losses.h)."""
+    _fields_ = [("x", _vp), ("s", _vp), ("t", _vp), ("mask_x", _vp), ("mask_s", _vp), ("mask_t", _vp),
+                ("mask_x_nstride", _i64), ("mask_s_nstride", _i64), ("mask_t_nstride", _i64), ("P", _i64),
+                ("dtype", _i32), ("N", _i32), ("C", _i32), ("flags", _i32), ("out", _vp), ("coef", _vp), ("ws", _vp)]
 
 
 # name -> (argtypes, restype); descriptors are passed by reference.
@@ -179,7 +187,18 @@ _PROTOS = {
     "mg_last_error": ([], ctypes.c_char_p),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
-_NO_STATUS = {"mg_wgrad_det_workspace", "mg_norm_apply2_supported", "mg_grad_slot_blocks", "mg_pack_job_blocks", "mg_sn_layer_blocks", "mg_stats_workspace", "mg_sizeof_desc", "mg_abi_version", "mg_last_error", "mg_noise_field_len", "mg_bicubic_ksize"}
+# The extension groups (include/michigan_hip/*.h): entry points beside the core table with the same obligations -- mirrored here, exported
+# by the library, guarded where they write device memory (tests/test_cabi_extensions.py).  Folding the two tables into one is a later
+# change: it moves MG_ABI_VERSION and the ledger tests that pin the core table.
+_EXT_PROTOS = {
+    "mg_ext_version": ([], _i32),
+    "mg_feat_moment_workspace": ([_i32, _i64, _i32], _i64),
+    "mg_feat_moment_loss_fwd": ([ctypes.POINTER(FeatMomentDesc), _vp], _i32),
+    "mg_feat_moment_loss_bwd": ([ctypes.POINTER(FeatMomentDesc), _vp, _vp, _vp, _vp], _i32),
+}
+EXTENSION_SYMBOLS = tuple(_EXT_PROTOS)
+_NO_STATUS = {"mg_wgrad_det_workspace", "mg_norm_apply2_supported", "mg_grad_slot_blocks", "mg_pack_job_blocks", "mg_sn_layer_blocks", "mg_stats_workspace", "mg_sizeof_desc", "mg_abi_version", "mg_last_error", "mg_noise_field_len", "mg_bicubic_ksize",
+              "mg_ext_version", "mg_feat_moment_workspace"}
 
 LIB_PATH = os.environ.get("MG_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmichigan_hip.so")   # MG_LIB: a measurement variant (tools/build_variant.py)
 
@@ -204,11 +223,14 @@ class HipBackend:
         # torch must already have loaded its libamdhip64 so that we bind to the same runtime.
         import torch  # noqa: F401
         self._lib = ctypes.CDLL(path)
-        for fn, (argtypes, restype) in _PROTOS.items():
-            f = getattr(self._lib, fn)          # AttributeError if a symbol is missing
-            f.argtypes, f.restype = argtypes, restype
+        for table in (_PROTOS, _EXT_PROTOS):
+            for fn, (argtypes, restype) in table.items():
+                f = getattr(self._lib, fn)          # AttributeError if a symbol is missing
+                f.argtypes, f.restype = argtypes, restype
         if self._lib.mg_abi_version() != MG_ABI_VERSION:
             raise RuntimeError("libmichigan_hip.so ABI version mismatch")
+        if self._lib.mg_ext_version() != MG_EXT_FEATURE_LOSSES:
+            raise RuntimeError("libmichigan_hip.so extension-group version mismatch (michigan_hip/feature_losses.h)")
         if (self._lib.mg_sizeof_desc(0) != ctypes.sizeof(ConvDesc) or self._lib.mg_sizeof_desc(1) != ctypes.sizeof(WgradDesc)
                 or self._lib.mg_sizeof_desc(2) != ctypes.sizeof(GradSlot) or self._lib.mg_sizeof_desc(3) != ctypes.sizeof(PackJob)
                 or self._lib.mg_sizeof_desc(4) != ctypes.sizeof(SnLayer) or self._lib.mg_sizeof_desc(5) != ctypes.sizeof(NormApply2Desc)
@@ -216,12 +238,12 @@ class HipBackend:
             raise RuntimeError("ctypes mirror of the descriptor structs is out of sync with include/michigan_hip.h")
 
     def __getattr__(self, fn):
-        if fn not in _PROTOS:
+        if fn not in _PROTOS and fn not in _EXT_PROTOS:
             raise AttributeError(fn)
         raw = getattr(self._lib, fn)
         if fn in _NO_STATUS:
             return raw
-        by_ref = fn in ("mg_conv_taps", "mg_conv_wgrad", "mg_norm_bwd_apply2", "mg_nearest_pyramid")
+        by_ref = fn in ("mg_conv_taps", "mg_conv_wgrad", "mg_norm_bwd_apply2", "mg_nearest_pyramid", "mg_feat_moment_loss_fwd", "mg_feat_moment_loss_bwd")
 
         def call(*args):
             if by_ref:

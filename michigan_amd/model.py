@@ -11,12 +11,17 @@ the benchmark's history were recorded without them.  With `unpairTrain` the seco
 (train.py:41-90 runs every epoch at `curr_step = 2` on unpaired data, then at 1 on paired data): at step 2 the discriminator
 is a second network `netD2` with its own Adam (pix2pix_model.py:147-150,568-572, pix2pix_trainer.py:61-77) and the generator
 objective is GAN + ORIENT (+ CONFIDENCE) + hairAvgLab + background (pix2pix_model.py:352-363), the last two as one fused
-pass (mg_hair_lab_*).  Style / content, balance_Lab and the blender are outside this tier's scope.
+pass (mg_hair_lab_*).  The style / content terms (pix2pix_model.py:309-319, on by default in the reference, switched off by the
+README command and by `default_options()`) are fused feature-moment passes over the VGG taps (mg_feat_moment_loss_*), computed at
+`curr_step == 1` whether or not the reference is the target, on the tower pass the VGG loss already pays for.  balance_Lab and the
+blender are outside this tier's scope.
 
 Differences that do not change results (SURVEY.md section 8a "parity-preserving minimum"):
   * the discriminator's parameters do not require grad during the generator step (their
     gradients are zeroed before use in the reference, pix2pix_trainer.py:64);
-  * the StyleContent VGG passes whose outputs the README flags discard are not executed.
+  * the StyleContent VGG passes whose outputs the flags discard are not executed, and the style / content terms share the VGG
+    loss's tower (the reference owns two towers with the same pretrained weights): vgg(fake) runs once for both, vgg(image_tag) is
+    the VGG loss's, the one added pass is vgg(image_ref) under no_grad when style is on.
 """
 from __future__ import annotations
 
@@ -70,6 +75,9 @@ def default_options(**over) -> argparse.Namespace:
         # here so that the recorded fixtures and benchmark numbers keep their objective -- switch them on per run
         no_lab_loss=True, no_rgb_loss=True, no_background_loss=True, lambda_lab=1.0, lambda_rgb=1.0, lambda_background=1.0,
         balance_Lab=False,
+        # style / content (pix2pix_model.py:309-319; on by default in the reference, off in the README command): off here for the same
+        # reason as the colour terms
+        no_style_loss=True, no_content_loss=True, lambda_style=1.0, lambda_content=1.0,
         # the unpaired training stage (train_options.py:38-41): netD2 + hairAvgLab at curr_step == 2
         unpairTrain=False, lambda_hairavglab=1.0, same_netD_model=False,
     )
@@ -98,6 +106,12 @@ class Pix2PixModel(nn.Module):
                 raise NotImplementedError("Lab colour loss: the balance_Lab weighting is not implemented")
             if getattr(opt, "unpairTrain", False):
                 self.criterionHairAvgLab = networks.HairAvgLabLoss(opt)
+            if not (getattr(opt, "no_style_loss", True) and getattr(opt, "no_content_loss", True)):
+                shared = self.criterionVGG.vgg if not opt.no_vgg_loss else None
+                self.criterionStyleContent = networks.StyleContentLoss(opt, vgg=shared)
+                dt = getattr(opt, "compute_dtype", None)
+                if shared is None and dt is not None:
+                    self.criterionStyleContent.vgg.compute_dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}.get(dt, dt)
         self.netIG = None
         if getattr(opt, "inpaint_orient", False):
             self.netIG = networks.define_IG(opt).eval()          # frozen (pix2pix_model.py:196-198)
@@ -176,6 +190,7 @@ class Pix2PixModel(nn.Module):
             if d is not None:
                 for k in ("_mg_input_cache", "_mg_mask_chain", "_mg_wide_edge", "_mg_label_src"):
                     d.pop(k, None)
+        self.__dict__.pop("_mg_style_masks", None)
 
     # -- networks -------------------------------------------------------------------
     def zeros_padding(self, t):
@@ -310,13 +325,35 @@ class Pix2PixModel(nn.Module):
             ref_is_tag = self._resolve_flag(pending)
             if self.opt.curr_step == 1 and ref_is_tag and not self.opt.no_ganFeat_loss:
                 losses["GAN_Feat"] = self.criterionGANFeat(pred_fake, pred_real, label)
+        style_on = self.opt.curr_step == 1 and not getattr(self.opt, "no_style_loss", True)
+        content_on = self.opt.curr_step == 1 and not getattr(self.opt, "no_content_loss", True)
+        x_feats = None
+        if style_on or content_on:
+            x_feats = self.criterionStyleContent.vgg(fake)        # ONE tower pass over the generated image for VGG, style and content
         if self.opt.curr_step == 1 and ref_is_tag:
             if not self.opt.no_vgg_loss:
                 if y_feats is not None:
                     main.wait_event(y_ev)
                     for t in y_feats:
                         t.record_stream(main)
-                losses["VGG"] = _scaled(self.criterionVGG(fake, d["image_tag"], label, y_feats=y_feats), self.opt.lambda_vgg)
+                elif content_on:
+                    with torch.no_grad():
+                        y_feats = self.criterionVGG.vgg(d["image_tag"])       # the pass VGGLoss would run itself, kept for the content term
+                losses["VGG"] = _scaled(self.criterionVGG(fake, d["image_tag"], label, y_feats=y_feats, x_feats=x_feats), self.opt.lambda_vgg)
+        if style_on or content_on:
+            # style / content (pix2pix_model.py:309-319): whether or not the reference is the target
+            masks = None
+            if getattr(self.opt, "remove_background", False):
+                masks = self.__dict__.get("_mg_style_masks")
+                if masks is None:                                 # the resized labels depend on the inputs alone: once per step
+                    masks = self.__dict__["_mg_style_masks"] = self.criterionStyleContent.resized_labels(
+                        d["input_ref"][:, 1:2], d["input_tag"][:, 1:2], [f.shape[2:] for f in x_feats])
+            loss_c, loss_s = self.criterionStyleContent(fake, d["image_ref"], d["image_tag"], d["input_ref"][:, 1:2], d["input_tag"][:, 1:2],
+                                                        fake_feats=x_feats, content_feats=y_feats, masks=masks, style=style_on, content=content_on)
+            if content_on:
+                losses["content"] = _scaled(loss_c, getattr(self.opt, "lambda_content", 1.0))
+            if style_on:
+                losses["style"] = _scaled(loss_s, getattr(self.opt, "lambda_style", 1.0))
         if not getattr(self.opt, "no_orient_loss", True) and "ORIENT" not in losses:
             orient, conf = self.criterionOrient(fake, d["orient"], d["input_tag"])
             losses["ORIENT"] = _scaled(orient, self.opt.lambda_orient)

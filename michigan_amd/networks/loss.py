@@ -3,9 +3,9 @@
 Reductions run in fp32 on whatever dtype the discriminator / VGG towers produced, as fused HIP launches: the hinge GAN
 loss with its wide-edge weight mask (mg_hinge_*, mg_wide_edge_weight), discriminator feature matching and the VGG taps
 (mg_l1_mean_*), the Gabor orientation loss (mg_gabor_argmax_*), and the image-space Lab colour / background / RGB L1
-terms as one pass (mg_color_loss_*), and the unpaired stage's hair-average Lab term (mg_hair_lab_*, fused with the background
-term in the model).  Style / content and the balance_Lab weighting are out of scope; style / content
-stay the reference's own classes under michigan_amd.dropin."""
+terms as one pass (mg_color_loss_*), the unpaired stage's hair-average Lab term (mg_hair_lab_*, fused with the background
+term in the model), and the style / content terms as fused feature-moment passes over the VGG taps (mg_feat_moment_loss_*).  The
+balance_Lab weighting is out of scope; under michigan_amd.dropin style / content stay the reference's own class."""
 from __future__ import annotations
 
 import math
@@ -160,12 +160,14 @@ class VGGLoss(nn.Module):
         lab = F.interpolate(label, size=input.shape[2:], mode="nearest")
         return F.l1_loss(input * lab, target * lab, reduction="sum") / (lab.sum() * input.shape[1] + 1e-5)
 
-    def forward(self, x, y, label=None, y_feats=None):
-        """`y_feats`: the (detached) tower features of y when the caller already has them (model.py computes them on the side stream)."""
+    def forward(self, x, y, label=None, y_feats=None, x_feats=None):
+        """`y_feats`: the (detached) tower features of y when the caller already has them (model.py computes them on the side stream);
+        `x_feats`: the tower features of x, with their graph, when the style / content terms share the pass."""
         if y_feats is None:
             with torch.no_grad():
                 y_feats = self.vgg(y)
-        x_feats = self.vgg(x)
+        if x_feats is None:
+            x_feats = self.vgg(x)
         vals = []
         for a, b in zip(x_feats, y_feats):
             if getattr(self.opt, "remove_background", False):
@@ -256,3 +258,63 @@ class HairAvgLabLoss(nn.Module):
 
     def forward(self, fake, real, mask_fake, mask_real):
         return ops.hair_lab_losses(_image_nhwc(fake), real, mask_fake.detach()[:, 0], mask_real.detach()[:, 0], flags=ops.HAIR_LAB)[0]
+
+
+class StyleContentLoss(nn.Module):
+    """Content and style terms of the generator objective (reference: loss.py:624-711): `forward` returns (loss_c, loss_s) like the
+    reference.  Content is the mean squared error between the relu5_1 features of the generated and of the content image; style sums,
+    over the five VGG19 taps, the MSE of the per-(sample, channel) means plus the MSE of the standard deviations of the generated and
+    the style image's features.  One fused pass per tap (ops.feat_moment_loss).
+
+    Under `opt.remove_background` the labels [N, 1, H, W] are resized to each tap with nearest sampling and their VALUE multiplies.
+    loss.py:692-693 is reproduced literally: the FAKE features' moments are taken under the STYLE label and the style features' under
+    the CONTENT label (the reference passes `style_label` to the first operand of calc_style_loss, which is the fake tap); the content
+    term is taken under the content label.
+
+    `vgg`: a tower to share (the reference owns a second one with the same pretrained weights).  `fake_feats` / `content_feats`: the
+    tower's features of fake_image (with their graph) / content_image when the caller already has them; `masks`: the resized labels
+    `resized_labels` returned for these inputs (they depend on the inputs alone: the model builds them once per step)."""
+
+    def __init__(self, opt=None, vgg=None):
+        super().__init__()
+        if vgg is not None:
+            self.__dict__["vgg"] = vgg                            # shared with its owner (VGGLoss): not registered a second time
+        else:
+            self.vgg = VGG19()
+            if torch.cuda.is_available():
+                self.vgg = self.vgg.cuda()
+        self.opt = opt
+
+    @staticmethod
+    def resized_labels(style_label, content_label, sizes):
+        """[(style plane, content plane) fp32 [N, h, w]] for every (h, w) of `sizes`: F.interpolate(label, size, mode='nearest')."""
+        out = []
+        for size in sizes:
+            out.append(tuple(F.interpolate(lab.detach().float(), size=size, mode="nearest")[:, 0] for lab in (style_label, content_label)))
+        return out
+
+    def forward(self, fake_image, style_image, content_image, style_label=None, content_label=None, fake_feats=None, content_feats=None,
+                masks=None, style=True, content=True):
+        if fake_feats is None:
+            fake_feats = self.vgg(fake_image)
+        last = len(fake_feats) - 1
+        with torch.no_grad():
+            style_feats = self.vgg(style_image) if style else None
+            if content and content_feats is None:
+                content_feats = self.vgg(content_image)
+        if getattr(self.opt, "remove_background", False) and masks is None:
+            masks = self.resized_labels(style_label, content_label, [f.shape[2:] for f in fake_feats])
+        loss_c, vals = 0, []
+        for i, x in enumerate(fake_feats):
+            flags = (ops.FEAT_STYLE if style else 0) | (ops.FEAT_CONTENT if content and i == last else 0)
+            if not flags:
+                continue
+            m_style, m_content = masks[i] if masks is not None else (None, None)
+            s, c = ops.feat_moment_loss(x, style_feats[i] if style else None, content_feats[i] if flags & ops.FEAT_CONTENT else None,
+                                        m_style, m_content, m_content, flags=flags)
+            if flags & ops.FEAT_STYLE:
+                vals.append(s)
+            if flags & ops.FEAT_CONTENT:
+                loss_c = c
+        loss_s = ops.weighted_sum(vals, [1.0] * len(vals)) if vals else 0
+        return loss_c, loss_s

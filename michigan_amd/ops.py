@@ -1991,6 +1991,102 @@ def hair_lab_losses(fake: torch.Tensor, image_ref: Optional[torch.Tensor], hair_
     return _HairLabLossFn.apply(fake, image_ref, hair_tag, hair_ref, image_tag, back, flags)
 
 
+FEAT_STYLE, FEAT_CONTENT = 1, 2                       # `flags` bits of mg_feat_moment_loss_*
+
+
+def _feat_desc(x, s, t, masks, flags, out=None, coef=None, ws=None):
+    d = C.FeatMomentDesc()
+    n, h, w, c = x.shape
+    d.x, d.s, d.t = x.data_ptr(), (s.data_ptr() if s is not None else None), (t.data_ptr() if t is not None else None)
+    for name, m in zip(("mask_x", "mask_s", "mask_t"), masks):
+        if m is not None:
+            ptr, stride = _plane_args(m)
+            setattr(d, name, ptr)
+            setattr(d, name + "_nstride", stride)
+    d.P, d.dtype, d.N, d.C, d.flags = h * w, _dt(x), n, c, flags
+    d.out, d.coef, d.ws = (None if out is None else out.data_ptr()), coef.data_ptr(), (None if ws is None else ws.data_ptr())
+    return d
+
+
+class _FeatMomentLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, s, t, mask_x, mask_s, mask_t, flags):
+        x = _nhwc(x)
+        n, h, w, c = x.shape
+        out = torch.empty(2, dtype=torch.float32, device=x.device)
+        coef = torch.empty(4 * n * c, dtype=torch.float32, device=x.device)
+        ws = torch.empty(int(C.backend().mg_feat_moment_workspace(n, h * w, c)), dtype=torch.uint8, device=x.device)
+        C.backend().mg_feat_moment_loss_fwd(_feat_desc(x, s, t, (mask_x, mask_s, mask_t), flags, out, coef, ws), _stream(x))
+        ctx.save_for_backward(x, t, mask_x, mask_t, coef)
+        ctx.flags = flags
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_style, g_content):
+        x, t, mask_x, mask_t, coef = ctx.saved_tensors
+        if g_style is None and g_content is None:
+            return (None,) * 7
+        fix = lambda g: None if g is None else (g if g.dtype == torch.float32 else g.float())
+        g_style, g_content = fix(g_style), fix(g_content)
+        d = torch.empty_like(x)
+        C.backend().mg_feat_moment_loss_bwd(_feat_desc(x, None, t, (mask_x, None, mask_t), ctx.flags, coef=coef), _p(g_style), _p(g_content),
+                                            _p(d), _stream(x))
+        return (d,) + (None,) * 6
+
+
+def feat_moment_loss(x: torch.Tensor, s: Optional[torch.Tensor], t: Optional[torch.Tensor] = None, mask_x: Optional[torch.Tensor] = None,
+                     mask_s: Optional[torch.Tensor] = None, mask_t: Optional[torch.Tensor] = None, flags: int = FEAT_STYLE):
+    """(style, content) of StyleContentLoss on ONE VGG tap (loss.py:624-694): x the fake features (gets the gradient), s the style
+    features, t the content features -- NCHW [N, C, h, w] bf16 / fp32; the towers' NCHW views of NHWC storage are read in place, a plain
+    contiguous NCHW tensor costs one copy.  style = MSE of the per-(sample, channel) means + MSE of the standard deviations of x and s,
+    content = MSE(x, t).  mask_x / mask_s / mask_t: fp32 [N, h, w] planes at the features' resolution (`remove_background`: x under
+    mask_x, s under mask_s, content under mask_t; the mask VALUE multiplies); None is the unmasked form, mask_x and mask_s come together.
+    `flags`: FEAT_STYLE | FEAT_CONTENT; a term not selected is 0, costs nothing and its operands may be None.  Two fp32 scalars (views
+    of one tensor), gradient to x only.  Two launches forward, one backward."""
+    flags = int(flags)
+    if not 1 <= flags <= 3:
+        raise ValueError("feat_moment_loss: flags must select at least one of FEAT_STYLE, FEAT_CONTENT")
+    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"feat_moment_loss: expected NCHW bf16 / fp32 features, got {tuple(x.shape)} {x.dtype}")
+    n, c, h, w = x.shape
+    if c % (8 if x.dtype == torch.bfloat16 else 4):
+        raise ValueError(f"feat_moment_loss: C = {c} is not a multiple of {8 if x.dtype == torch.bfloat16 else 4} (16 bytes of channels per lane)")
+
+    def feats(f, name):
+        if f is None:
+            raise ValueError("feat_moment_loss: %s is needed for the selected terms" % name)
+        if tuple(f.shape) != (n, c, h, w):
+            raise ValueError(f"feat_moment_loss: {name} {tuple(f.shape)} does not match the fake features {tuple(x.shape)}")
+        f = f.detach()
+        return _nhwc((f if f.dtype == x.dtype else f.to(x.dtype)).permute(0, 2, 3, 1))
+
+    def plane(m, name):
+        m = m.detach()
+        if m.dtype != torch.float32:
+            m = m.float()
+        if tuple(m.shape) != (n, h, w):
+            raise ValueError(f"feat_moment_loss: {name} {tuple(m.shape)} does not match the features")
+        return m if (m.stride(2) == 1 and m.stride(1) == m.shape[2]) else m.contiguous()
+
+    if flags & FEAT_STYLE:
+        s = feats(s, "the style features")
+        if (mask_x is None) != (mask_s is None):
+            raise ValueError("feat_moment_loss: mask_x and mask_s come together")
+        if mask_x is not None:
+            mask_x, mask_s = plane(mask_x, "mask_x"), plane(mask_s, "mask_s")
+        elif h * w < 2:
+            raise ValueError("feat_moment_loss: the unbiased variance needs at least two pixels")
+    else:
+        s = mask_x = mask_s = None
+    if flags & FEAT_CONTENT:
+        t = feats(t, "the content features")
+        mask_t = plane(mask_t, "mask_t") if mask_t is not None else None
+    else:
+        t = mask_t = None
+    return _FeatMomentLossFn.apply(x.permute(0, 2, 3, 1), s, t, mask_x, mask_s, mask_t, flags)
+
+
 class _WeightedSumFn(torch.autograd.Function):
     """sum_k w_k * v_k of K scalar tensors as THREE launches forward (stack, mul, sum) and ONE backward (g * w), whatever K: the loss
     modules used to chain `total = total + val * w` -- 2 launches forward and 2 backward per term, ~100 five-microsecond

@@ -1,8 +1,10 @@
 """Launch census of one training step WITHOUT a GPU: torch (aten) ops that would each be a kernel launch on the device, and C-ABI
 calls (= HIP launches), per phase of the step.  Runs the trainer on the contract emulator at a small size -- the launch COUNT of the
 host stack does not depend on the tensor sizes (same code paths), only the dispatch heuristics inside the library do (those are
-counted as one C-ABI call each).     python tools/count_launches.py [--by-op] [--where] [--unpaired]
+counted as one C-ABI call each).     python tools/count_launches.py [--by-op] [--where] [--unpaired | --style]
 --unpaired: the step of the unpaired stage (unpairTrain, curr_step = 2: netD2, GAN + ORIENT + hairAvgLab + background) instead.
+--style: the default step with the style and content terms on (phase G.loss_style: one mg_feat_moment_loss_fwd per tap = two
+launches each, the tower pass over image_ref; their backward calls are in G.backward).
 
 View-like aten ops (no kernel) are not counted; ops issued INSIDE the emulator (its own arithmetic) are not counted either.
 """
@@ -56,7 +58,7 @@ class CountingBackend:
     """Proxy in front of the emulator: every C-ABI call that launches is one HIP launch; aten ops inside it do not count."""
     NO_LAUNCH = ("mg_stats_workspace", "mg_abi_version", "mg_sizeof_desc", "mg_last_error", "mg_grad_slot_blocks", "mg_set_option",
                  "mg_norm_apply2_supported", "mg_nearest_table", "mg_bicubic_table", "mg_bicubic_ksize", "mg_orient_rgb_table",
-                 "mg_noise_field_len", "mg_inputs_set_option", "mg_conv_workspace")
+                 "mg_noise_field_len", "mg_inputs_set_option", "mg_conv_workspace", "mg_feat_moment_workspace", "mg_ext_version")
 
     def __init__(self, inner, census):
         self._inner, self._census = inner, census
@@ -87,11 +89,17 @@ def main():
     torch.set_num_threads(4)
     census = Census()
     unpaired = "--unpaired" in sys.argv
+    style = "--style" in sys.argv and not unpaired
     if unpaired:
-        from hair_lab_emulator import HairLabEmulator
-    _cabi.set_backend(CountingBackend(HairLabEmulator() if unpaired else EmulatorBackend(), census))
+        from hair_lab_emulator import HairLabEmulator as Emulator
+    elif style:
+        from style_loss_emulator import StyleLossEmulator as Emulator
+    else:
+        Emulator = EmulatorBackend
+    _cabi.set_backend(CountingBackend(Emulator(), census))
     torch.manual_seed(0)
-    opt = default_options(ngf=8, ndf=8, crop_size=128, gpu_ids=[], compute_dtype="fp32", unpairTrain=unpaired, curr_step=2 if unpaired else 1)
+    opt = default_options(ngf=8, ndf=8, crop_size=128, gpu_ids=[], compute_dtype="fp32", unpairTrain=unpaired, curr_step=2 if unpaired else 1,
+                          no_style_loss=not style, no_content_loss=not style)
     tr = Pix2PixTrainer(opt)
     data = synth_batch(2, 128, seed=1234, unpaired=unpaired)
     m = tr.pix2pix_model
@@ -109,7 +117,16 @@ def main():
         terms = {"a": lg}
         if not unpaired:
             ph("G.loss_feat"); terms["b"] = m.criterionGANFeat(pf, pr, label)
-            ph("G.loss_vgg"); terms["c"] = m.criterionVGG(fake, d["image_tag"], label) * opt.lambda_vgg
+            ph("G.loss_vgg")
+            x_feats = y_feats = None
+            if style:                                     # as compute_generator_loss: one pass over fake, image_tag's features kept
+                x_feats = m.criterionVGG.vgg(fake)
+                with torch.no_grad():
+                    y_feats = m.criterionVGG.vgg(d["image_tag"])
+            terms["c"] = m.criterionVGG(fake, d["image_tag"], label, y_feats=y_feats, x_feats=x_feats) * opt.lambda_vgg
+            if style:
+                ph("G.loss_style")
+                terms["g"], terms["h"] = m.criterionStyleContent(fake, d["image_ref"], d["image_tag"], fake_feats=x_feats, content_feats=y_feats)
         ph("G.loss_orient"); terms["d"] = m.criterionOrient(fake, d["orient"], d["input_tag"])[0] * opt.lambda_orient
         if unpaired:
             from michigan_amd import ops
@@ -145,14 +162,14 @@ def main():
         else:
             g_step(False); d_step(False)
     phases = sorted(set(census.aten) | set(census.hip), key=lambda p: (p[0] != "G", p))
-    order = ["G.zero_grad", "G.preprocess", "G.generator_fwd", "G.discriminate", "G.loss_gan", "G.loss_feat", "G.loss_vgg", "G.loss_orient",
+    order = ["G.zero_grad", "G.preprocess", "G.generator_fwd", "G.discriminate", "G.loss_gan", "G.loss_feat", "G.loss_vgg", "G.loss_style", "G.loss_orient",
              "G.loss_hair_lab", "G.loss_sum", "G.backward", "G.optimizer", "D.zero_grad", "D.preprocess", "D.generator_fwd", "D.discriminate", "D.loss",
              "D.backward", "D.optimizer"]
     ta = th = 0
     print("%-18s %6s %6s" % ("phase", "aten", "hip"))
     for p in order + [p for p in phases if p not in order]:
         a, h = census.aten.get(p, 0), census.hip.get(p, 0)
-        if p in ("G.loss_feat", "G.loss_vgg", "G.loss_hair_lab") and p not in phases:
+        if p in ("G.loss_feat", "G.loss_vgg", "G.loss_style", "G.loss_hair_lab") and p not in phases:
             continue                                      # a term this kind of step does not have
         ta, th = ta + a, th + h
         print("%-18s %6d %6d" % (p, a, h))
