@@ -17,9 +17,9 @@ exact in ANY order and the only rounding left is the store conversion: every out
   * ``ops.conv_wgrad`` on its own over the guard-band table's WGRAD_PATHS, with fp32 atomics and with ops.set_deterministic(True),
     with and without the fused bias gradient: both orders must equal the reference, and so each other.
   * the SPADE epilogue (``ops.spade_modulate`` with a GIVEN mean / rstd; one x_up case through spade_modulate_pair): h and the
-    gradients with respect to actv, both weights and both biases.  NOT compared: the gradient with respect to x -- the norm
-    backward divides by the pixel count and reads (1 + gamma) back from bf16, it is not an exact quantity and stays with the
-    max-norm tests.
+    gradients with respect to actv, both weights and both biases.  The gradient with respect to x is not compared HERE: it is
+    held bit for bit in tests/test_gpu_census.py, whose caller's count is a power of two and whose reference reads (1 + gamma)
+    in its stored form, together with the norm backward's reductions and applies on their own.
 
 The reference is torch on the CPU in float64; the chip-filling cases use the fp32 CPU convolution, which returns the same bits once
 the exactness precondition holds (tests/test_exact_operands.py asserts that equality).  Preconditions (exactness, >= 5 % of bf16
