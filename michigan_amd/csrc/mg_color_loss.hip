@@ -14,6 +14,7 @@
 #include "mg_common.h"
 #include "mg_launch.h"
 #include "mg_lab.h"
+#include "mg_reduce.h"
 
 // No fused multiply-add contraction in this file: a - b of two products that are equal must be exactly 0 (sign(0) = 0 where the
 // generated pixel equals the target), and a contracted fma(x, y, -round(x * y)) would leave the product's rounding error instead.
@@ -29,7 +30,7 @@ __global__ __launch_bounds__(256) void color_loss_partial_kernel(const T* __rest
                                                                  int flags, float* __restrict__ ws)
 {
     __shared__ float red[3][4];
-    float s_lab = 0.f, s_rgb = 0.f, s_bg = 0.f;
+    float s[3] = {0.f, 0.f, 0.f};                                 // lab, rgb, background
     const int64_t total = (int64_t)N * HW;
     for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int n = (int)(i / HW);
@@ -42,23 +43,16 @@ __global__ __launch_bounds__(256) void color_loss_partial_kernel(const T* __rest
             float af, bf, ar, br;
             cl_ab(xf, af, bf);
             cl_ab(xr, ar, br);
-            s_lab += fabsf(af - ar) + fabsf(bf - br);
+            s[0] += fabsf(af - ar) + fabsf(bf - br);
         }
-        if (flags & 2) s_rgb += fabsf(xf[0] - xr[0]) + fabsf(xf[1] - xr[1]) + fabsf(xf[2] - xr[2]);
+        if (flags & 2) s[1] += fabsf(xf[0] - xr[0]) + fabsf(xf[1] - xr[1]) + fabsf(xf[2] - xr[2]);
         if (flags & 4) {
             const float m = back[(int64_t)n * back_nstride + pix];
-            s_bg += fabsf(xf[0] * m - xr[0] * m) + fabsf(xf[1] * m - xr[1] * m) + fabsf(xf[2] * m - xr[2] * m);
+            s[2] += fabsf(xf[0] * m - xr[0] * m) + fabsf(xf[1] * m - xr[1] * m) + fabsf(xf[2] * m - xr[2] * m);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s_lab += __shfl_down(s_lab, o, 64); s_rgb += __shfl_down(s_rgb, o, 64); s_bg += __shfl_down(s_bg, o, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s_lab; red[1][threadIdx.x >> 6] = s_rgb; red[2][threadIdx.x >> 6] = s_bg; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        float t = 0.f;
-        for (int w = 0; w < 4; ++w) t += red[threadIdx.x][w];
-        ws[threadIdx.x * CL_BLOCKS + blockIdx.x] = t;
-    }
+    const float t = mg_block_sum_to<MgJoin::LeftToRight>(s, red);
+    if (threadIdx.x < 3) ws[threadIdx.x * CL_BLOCKS + blockIdx.x] = t;
 }
 
 __global__ __launch_bounds__(256) void color_loss_final_kernel(const float* __restrict__ ws, int nblk, double inv_lab, double inv_rgb, float* __restrict__ out)
@@ -67,12 +61,7 @@ __global__ __launch_bounds__(256) void color_loss_final_kernel(const float* __re
     double s[3] = {0.0, 0.0, 0.0};
     for (int i = threadIdx.x; i < nblk; i += 256)
         for (int q = 0; q < 3; ++q) s[q] += (double)ws[q * CL_BLOCKS + i];
-    for (int q = 0; q < 3; ++q) red[q][threadIdx.x] = s[q];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + o];
-        __syncthreads();
-    }
+    mg_tree_sum_f64(s, red);
     if (threadIdx.x == 0) {
         out[0] = (float)(red[0][0] * inv_lab);                      // nn.L1Loss over Lab channels 1: -> N*2*H*W elements
         out[1] = (float)(red[1][0] * inv_rgb);                      // nn.L1Loss over N*3*H*W
@@ -119,19 +108,9 @@ __global__ __launch_bounds__(256) void color_loss_bwd_kernel(const T* __restrict
 #pragma unroll
             for (int c = 0; c < 3; ++c) d[c] += gb * m * cl_sign(xf[c] * m - xr[c] * m);
         }
-        T* __restrict__ o = dimg + i * C;
-        if ((C & 3) == 0) {
-            const f32x4_t v = {d[0], d[1], d[2], 0.f}, z = {0.f, 0.f, 0.f, 0.f};
-            ET<T>::store4(o, v);
-            for (int c = 4; c < C; c += 4) ET<T>::store4(o + c, z);
-        } else {
-            ET<T>::store1(o, d[0]); ET<T>::store1(o + 1, d[1]); ET<T>::store1(o + 2, d[2]);
-            for (int c = 3; c < C; ++c) ET<T>::store1(o + c, 0.f);
-        }
+        cl_store_rgb_grad(dimg + i * C, C, d);
     }
 }
-
-inline int cl_grid(int64_t pixels, int cap) { const int64_t g = (pixels + 255) / 256; return (int)(g > cap ? cap : g); }
 
 }  // namespace
 
@@ -149,7 +128,7 @@ extern "C" int mg_color_loss_fwd(const void* img, const float* real, int64_t rea
     MG_COLOR_CHECK("mg_color_loss_fwd");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t HW = (int64_t)H * W;
-    const int grid = cl_grid((int64_t)N * HW, CL_BLOCKS);
+    const int grid = mg_ew_grid((int64_t)N * HW, CL_BLOCKS);
     mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
         hipLaunchKernelGGL(color_loss_partial_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)img, real, real_nstride, back, back_nstride, N, HW, C, flags, ws); });
     MG_CHECK_LAUNCH("mg_color_loss_fwd");
@@ -167,7 +146,7 @@ extern "C" int mg_color_loss_bwd(const void* img, const float* real, int64_t rea
     MG_COLOR_CHECK("mg_color_loss_bwd");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t HW = (int64_t)H * W;
-    const int grid = cl_grid((int64_t)N * HW, 4096);
+    const int grid = mg_ew_grid((int64_t)N * HW, 4096);
     mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
         hipLaunchKernelGGL(color_loss_bwd_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)img, real, real_nstride, back, back_nstride, g_lab, g_rgb, g_back, N, HW, C, flags, (T*)dimg); });
     MG_CHECK_LAUNCH("mg_color_loss_bwd");

@@ -14,6 +14,7 @@
 //   feat_moment_bwd_kernel      dx in the features' dtype and layout from x, t, the masks and coef; reduces nothing
 #include "mg_common.h"
 #include "mg_launch.h"
+#include "mg_reduce.h"
 #include "michigan_hip/feature_losses.h"
 #include <limits.h>
 
@@ -102,13 +103,6 @@ template <> struct FV<uint16_t> {
 };
 template <typename T> __device__ __forceinline__ uint4 fm_load(const T* p) { return *reinterpret_cast<const uint4*>(p); }
 
-__device__ __forceinline__ double fm_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // MASKED: at least one mask pointer is given (a NULL one among them reads as 1).  Unmasked, sum m y = sum m^3 y = sum m^4 y: only
 // planes A1 and A4 are formed and the final kernel reads those.
 template <typename T, bool MASKED>
@@ -135,8 +129,8 @@ __global__ __launch_bounds__(256) void feat_moment_partial_kernel(const FmArgs a
     // ---- the chunk's masks: power sums in double and the first non-zero pixel of mask_x / mask_s (the pivots) ----
     if (tid < 2) piv[tid] = INT_MAX;
     __syncthreads();
+    double md[FM_MSUMS];
     {
-        double md[FM_MSUMS];
 #pragma unroll
         for (int i = 0; i < FM_MSUMS; ++i) md[i] = 0.0;
         int fx = INT_MAX, fs = INT_MAX;
@@ -153,15 +147,9 @@ __global__ __launch_bounds__(256) void feat_moment_partial_kernel(const FmArgs a
         }
         if (fx != INT_MAX) atomicMin(&piv[0], fx);
         if (fs != INT_MAX) atomicMin(&piv[1], fs);
-#pragma unroll
-        for (int i = 0; i < FM_MSUMS; ++i) {
-            md[i] = fm_wave_sum(md[i]);
-            if ((tid & 63) == 0) mred[i][tid >> 6] = md[i];
-        }
     }
-    __syncthreads();
-    if (ct == 0 && tid < FM_MSUMS)
-        a.msum[((int64_t)n * a.nchunks + ck) * FM_MSUMS + tid] = (mred[tid][0] + mred[tid][1]) + (mred[tid][2] + mred[tid][3]);
+    const double msum = mg_block_sum_to<MgJoin::Pairwise>(md, mred);        // its barrier also orders the pivots
+    if (ct == 0 && tid < FM_MSUMS) a.msum[((int64_t)n * a.nchunks + ck) * FM_MSUMS + tid] = msum;
     const int px = piv[0], ps = piv[1];
 
     const T* __restrict__ xb = (const T*)a.x + (int64_t)n * a.P * a.C + c;
@@ -265,22 +253,9 @@ __global__ __launch_bounds__(256) void feat_moment_partial_kernel(const FmArgs a
         }
     }
     if (content) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) qs += __shfl_down(qs, o, 64);
-        if ((tid & 63) == 0) qred[tid >> 6] = qs;
-        __syncthreads();
-        if (tid == 0) a.qsum[((int64_t)n * a.nchunks + ck) * a.ctiles + ct] = (qred[0] + qred[1]) + (qred[2] + qred[3]);
+        const float q = mg_block_sum_to<MgJoin::Pairwise>(qs, qred);
+        if (tid == 0) a.qsum[((int64_t)n * a.nchunks + ck) * a.ctiles + ct] = q;
     }
-}
-
-// sum of v over the workgroup's 256 threads in a fixed order; every thread gets it (scratch: 4 doubles, re-usable after the call)
-__device__ __forceinline__ double fm_block_sum(double v, double* scratch)
-{
-    v = fm_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);
 }
 
 __global__ __launch_bounds__(256) void feat_moment_final_kernel(const FmArgs a, int style_masked, int content_masked)
@@ -302,14 +277,10 @@ __global__ __launch_bounds__(256) void feat_moment_final_kernel(const FmArgs a, 
     tm[8] = 0.0;
     if (content && content_masked)
         for (int64_t i = tid; i < (int64_t)a.N * a.nchunks; i += 256) tm[8] += a.msum[i * FM_MSUMS + 8];
-#pragma unroll
-    for (int i = 0; i < FM_MSUMS; ++i) {
-        tm[i] = fm_wave_sum(tm[i]);
-        if ((tid & 63) == 0) mred[i][tid >> 6] = tm[i];
-    }
+    mg_put_wave_sums(tm, mred);
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < FM_MSUMS; ++i) tm[i] = (mred[i][0] + mred[i][1]) + (mred[i][2] + mred[i][3]);
+    for (int i = 0; i < FM_MSUMS; ++i) tm[i] = mg_join<MgJoin::Pairwise>(mred[i]);      // every thread needs all nine
     double two_over_den = 0.0, den = 1.0;
     if (content) {
         den = content_masked ? (double)a.C * tm[8] + 1e-5 : (double)a.N * P * (double)a.C;
@@ -368,7 +339,7 @@ __global__ __launch_bounds__(256) void feat_moment_final_kernel(const FmArgs a, 
         const f32x4_t v = {0.f, 0.f, 0.f, (float)two_over_den};
         ET<float>::store4(a.coef + 4 * ((int64_t)n * a.C + c), v);
     }
-    e = fm_block_sum(e, scratch);                                         // the chunk lanes 1..15 hold 0
+    e = mg_block_sum_all<MgJoin::Pairwise>(e, scratch);                   // the chunk lanes 1..15 hold 0
 
     // ---- arrival: the workgroup's sum is published, the last workgroup to arrive adds them all ----
     const int nblocks = gridDim.x * gridDim.y;
@@ -388,8 +359,8 @@ __global__ __launch_bounds__(256) void feat_moment_final_kernel(const FmArgs a, 
     double st = 0.0, q = 0.0;
     if (style) for (int i = tid; i < nblocks; i += 256) st += a.bsum[i];
     if (content) for (int64_t i = tid; i < (int64_t)a.N * a.nchunks * a.ctiles; i += 256) q += (double)a.qsum[i];
-    st = fm_block_sum(st, scratch);
-    q = fm_block_sum(q, scratch);
+    st = mg_block_sum_all<MgJoin::Pairwise>(st, scratch);
+    q = mg_block_sum_all<MgJoin::Pairwise>(q, scratch);
     if (tid == 0) {
         a.out[0] = style ? (float)(st / ((double)a.N * (double)a.C)) : 0.f;
         a.out[1] = content ? (float)(q / den) : 0.f;

@@ -19,6 +19,7 @@
 //                            (two-stage deterministic sums) and backward (d/d confidence response) -- ~45 launches per step before.
 #include "mg_common.h"
 #include "mg_launch.h"
+#include "mg_reduce.h"
 
 namespace {
 
@@ -161,6 +162,8 @@ __global__ __launch_bounds__(256) void bg_compose_kernel(const float* __restrict
 }
 
 // ---- orientation-loss tail -------------------------------------------------------------------------------------------------------
+constexpr int OL_BLOCKS = 1024;                                   // rows of the workspace: ws[term * OL_BLOCKS + block]
+
 __device__ __forceinline__ void orient_terms(float craw, int idx, const float* __restrict__ label, int label_ch, int64_t HW, int64_t pix,
                                              float hairv, float& confidence, float& d0, float& d1, float& f0, float& f1)
 {
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(256) void orient_loss_partial_kernel(const float* _
                                                                   float* __restrict__ ws)
 {
     __shared__ float red[3][4];
-    float s_abs = 0.f, s_log = 0.f, s_hair = 0.f;
+    float s[3] = {0.f, 0.f, 0.f};                                 // |d|, log(confidence) * hair, hair
     const int64_t total = (int64_t)N * HW;
     for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int n = (int)(i / HW);
@@ -189,19 +192,12 @@ __global__ __launch_bounds__(256) void orient_loss_partial_kernel(const float* _
         const float hv = hair[(int64_t)n * hair_nstride + pix];
         float cf, d0, d1, f0, f1;
         orient_terms(conf_raw[i], idx[i], label + (int64_t)n * label_nstride, label_ch, HW, pix, hv, cf, d0, d1, f0, f1);
-        s_abs += fabsf(d0) + fabsf(d1);
-        s_log += logf(fminf(fmaxf(cf, 0.001f), 1.f)) * hv;
-        s_hair += hv;
+        s[0] += fabsf(d0) + fabsf(d1);
+        s[1] += logf(fminf(fmaxf(cf, 0.001f), 1.f)) * hv;
+        s[2] += hv;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s_abs += __shfl_down(s_abs, o, 64); s_log += __shfl_down(s_log, o, 64); s_hair += __shfl_down(s_hair, o, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s_abs; red[1][threadIdx.x >> 6] = s_log; red[2][threadIdx.x >> 6] = s_hair; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        float t = 0.f;
-        for (int w = 0; w < 4; ++w) t += red[threadIdx.x][w];
-        ws[threadIdx.x * 1024 + blockIdx.x] = t;
-    }
+    const float t = mg_block_sum_to<MgJoin::LeftToRight>(s, red);
+    if (threadIdx.x < 3) ws[threadIdx.x * OL_BLOCKS + blockIdx.x] = t;
 }
 
 __global__ void orient_loss_final_kernel(const float* __restrict__ ws, int nblk, double inv_count, float* __restrict__ out)
@@ -209,13 +205,8 @@ __global__ void orient_loss_final_kernel(const float* __restrict__ ws, int nblk,
     __shared__ double red[3][256];
     double s[3] = {0.0, 0.0, 0.0};
     for (int i = threadIdx.x; i < nblk; i += 256)
-        for (int q = 0; q < 3; ++q) s[q] += (double)ws[q * 1024 + i];
-    for (int q = 0; q < 3; ++q) red[q][threadIdx.x] = s[q];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + o];
-        __syncthreads();
-    }
+        for (int q = 0; q < 3; ++q) s[q] += (double)ws[q * OL_BLOCKS + i];
+    mg_tree_sum_f64(s, red);
     if (threadIdx.x == 0) {
         out[0] = (float)(red[0][0] * inv_count);                    // F.l1_loss over N*2*H*W elements
         out[1] = (float)(-red[1][0] / red[2][0]);                   // -sum(log(conf) * hair) / sum(hair)
@@ -361,7 +352,7 @@ extern "C" int mg_orient_loss_fwd(const float* conf_raw, const uint8_t* idx, con
     MG_CHECK_ARG(conf_raw && idx && label && hair && out && ws, "mg_orient_loss_fwd: null pointer");
     MG_CHECK_ARG((label_ch == 1 || label_ch == 2) && N > 0 && HW > 0, "mg_orient_loss_fwd: bad geometry");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int grid = mg_ew_grid((int64_t)N * HW, 1024);
+    const int grid = mg_ew_grid((int64_t)N * HW, OL_BLOCKS);
     hipLaunchKernelGGL(orient_loss_partial_kernel, dim3(grid), dim3(256), 0, st, conf_raw, idx, label, label_ch, label_nstride, hair, hair_nstride, N, HW, ws);
     MG_CHECK_LAUNCH("mg_orient_loss_fwd");
     hipLaunchKernelGGL(orient_loss_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, grid, 1.0 / (2.0 * (double)N * (double)HW), out);

@@ -17,6 +17,7 @@
 // and written / read-modify-written as one contiguous 64*T-float run of the reference tensor.  HBM-bound: ~16 B per
 // gradient element (+4 B of W_sn for spectral-normed layers); no MFMA.
 #include "mg_common.h"
+#include "mg_reduce.h"
 
 namespace {
 
@@ -90,11 +91,8 @@ __global__ __launch_bounds__(256) void grad_sn_dot_kernel(const mg_grad_slot* __
         }
         acc += (double)part;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    const double t = mg_block_sum_to<MgJoin::LeftToRight>(acc, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
 // s[slot] = sum of the slot's per-workgroup partials in a FIXED order (one workgroup per slot): the value every rank of a
@@ -108,9 +106,7 @@ __global__ __launch_bounds__(256) void grad_sn_finish_kernel(const mg_grad_slot*
     const int b0 = (int)s.first_block;
     double acc = 0.0;
     for (int b = b0 + threadIdx.x; b < nblocks_total && block_slot[b] == (int)blockIdx.x; b += 256) acc += partial[b];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    mg_tree_sum_f64(acc, red);
     if (threadIdx.x == 0) *s.s = red[0];
 }
 

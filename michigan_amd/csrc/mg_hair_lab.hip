@@ -15,6 +15,7 @@
 #include "mg_common.h"
 #include "mg_launch.h"
 #include "mg_lab.h"
+#include "mg_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -64,21 +65,8 @@ __global__ __launch_bounds__(256) void hair_lab_partial_kernel(const T* __restri
             s[6] += fabsf(xf[0] * vb - tp[0] * vb) + fabsf(xf[1] * vb - tp[HW] * vb) + fabsf(xf[2] * vb - tp[2 * HW] * vb);
         }
     }
-#pragma unroll
-    for (int q = 0; q < HL_TERMS; ++q) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[q] += __shfl_down(s[q], o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < HL_TERMS; ++q) red[q][threadIdx.x >> 6] = s[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < HL_TERMS) {
-        float t = 0.f;
-        for (int w = 0; w < 4; ++w) t += red[threadIdx.x][w];
-        ws[((int64_t)threadIdx.x * N + n) * gridDim.x + blockIdx.x] = t;
-    }
+    const float t = mg_block_sum_to<MgJoin::LeftToRight>(s, red);
+    if (threadIdx.x < HL_TERMS) ws[((int64_t)threadIdx.x * N + n) * gridDim.x + blockIdx.x] = t;
 }
 
 // one workgroup; wave w owns samples w, w + 4, ...: lanes stride over the sample's partials, a fixed shuffle tree joins them
@@ -94,9 +82,7 @@ __global__ __launch_bounds__(256) void hair_lab_final_kernel(const float* __rest
         for (int q = 0; q < HL_TERMS; ++q) {
             double t = 0.0;
             for (int i = lane; i < bps; i += 64) t += (double)ws[((int64_t)q * N + n) * bps + i];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
-            s[q] = t;
+            s[q] = mg_wave_sum(t);
         }
         if (lane == 0) {
             if (flags & 1) {
@@ -112,8 +98,8 @@ __global__ __launch_bounds__(256) void hair_lab_final_kernel(const float* __rest
     if (lane == 0) { red[0][wave] = hair; red[1][wave] = bg; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        out[0] = (float)((red[0][0] + red[0][1] + red[0][2] + red[0][3]) * inv_hair);       // nn.L1Loss over [N, 2, 1, 1]
-        out[1] = (float)((red[1][0] + red[1][1] + red[1][2] + red[1][3]) * inv_back);       // mean over N*3*H*W, not divided by sum(m_b)
+        out[0] = (float)(mg_join<MgJoin::LeftToRight>(red[0]) * inv_hair);                  // nn.L1Loss over [N, 2, 1, 1]
+        out[1] = (float)(mg_join<MgJoin::LeftToRight>(red[1]) * inv_back);                  // mean over N*3*H*W, not divided by sum(m_b)
     }
 }
 
@@ -157,15 +143,7 @@ __global__ __launch_bounds__(256) void hair_lab_bwd_kernel(const T* __restrict__
 #pragma unroll
             for (int c = 0; c < 3; ++c) d[c] += gb * vb * cl_sign(xf[c] * vb - xr[c] * vb);
         }
-        T* __restrict__ o = op + pix * C;
-        if ((C & 3) == 0) {
-            const f32x4_t v = {d[0], d[1], d[2], 0.f}, z = {0.f, 0.f, 0.f, 0.f};
-            ET<T>::store4(o, v);
-            for (int c = 4; c < C; c += 4) ET<T>::store4(o + c, z);
-        } else {
-            ET<T>::store1(o, d[0]); ET<T>::store1(o + 1, d[1]); ET<T>::store1(o + 2, d[2]);
-            for (int c = 3; c < C; ++c) ET<T>::store1(o + c, 0.f);
-        }
+        cl_store_rgb_grad(op + pix * C, C, d);
     }
 }
 

@@ -45,4 +45,18 @@ __device__ __forceinline__ void cl_load_rgb(const T* __restrict__ p, int C, floa
     else { x[0] = ET<T>::load1(p); x[1] = ET<T>::load1(p + 1); x[2] = ET<T>::load1(p + 2); }
 }
 
+// the gradient of one generated pixel: d in channels 0..2, zero in the padding channels; quads when the pixel is quad-aligned
+template <typename T>
+__device__ __forceinline__ void cl_store_rgb_grad(T* __restrict__ o, int C, const float d[3])
+{
+    if ((C & 3) == 0) {
+        const f32x4_t v = {d[0], d[1], d[2], 0.f}, z = {0.f, 0.f, 0.f, 0.f};
+        ET<T>::store4(o, v);
+        for (int c = 4; c < C; c += 4) ET<T>::store4(o + c, z);
+    } else {
+        ET<T>::store1(o, d[0]); ET<T>::store1(o + 1, d[1]); ET<T>::store1(o + 2, d[2]);
+        for (int c = 3; c < C; ++c) ET<T>::store1(o + c, 0.f);
+    }
+}
+
 }  // namespace

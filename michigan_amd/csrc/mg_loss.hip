@@ -14,6 +14,7 @@
 // Index work on tiny maps: one thread per element, no LDS tiling needed (each 67x67 map is 18 KiB).
 #include "mg_common.h"
 #include "mg_launch.h"
+#include "mg_reduce.h"
 
 namespace {
 
@@ -65,9 +66,7 @@ __global__ __launch_bounds__(1024) void hinge_fwd_kernel(const T* __restrict__ x
         if (weight) v *= weight[i];
         s += (double)v;
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    mg_tree_sum_f64(s, red);
     if (threadIdx.x == 0) out[0] = (float)(-red[0] / (double)n);
 }
 

@@ -5,6 +5,7 @@
 // One thread = one quad (4 consecutive channels) -> 8 B (bf16) / 16 B (f32) accesses.
 #include "mg_common.h"
 #include "mg_launch.h"
+#include "mg_reduce.h"
 
 namespace {
 
@@ -273,20 +274,15 @@ __global__ __launch_bounds__(MG_NTHR) void l1_partial_kernel(const T* __restrict
 #pragma unroll
         for (int j = 0; j < 4; ++j) s += fabsf(x[j] - y[j]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { float t = 0.f; for (int w = 0; w < MG_NTHR / 64; ++w) t += red[w]; partial[blockIdx.x] = t; }
+    const float t = mg_block_sum_to<MgJoin::LeftToRight>(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 __global__ void l1_final_kernel(const float* __restrict__ partial, int n, double inv_numel, float* __restrict__ out)
 {
     __shared__ double red[256];
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    mg_tree_sum_f64(s, red);
     if (threadIdx.x == 0) out[0] = (float)(red[0] * inv_numel);
 }
 template <typename T>

@@ -5,21 +5,9 @@
 // The eager form is ~16 launches per layer forward and ~10 weight-sized passes backward (4.4 ms of a 87 ms step,
 // tools/sn_cost.py); this is 5 launches forward and 2 backward.
 #include "mg_common.h"
+#include "mg_reduce.h"
 
 namespace {
-
-__device__ __forceinline__ float block_sum(float v, float* red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int i = 0; i < nw; ++i) t += red[i];
-    return t;
-}
 
 // dst (and dst2) = t / max(||t||_2, eps);  sigma = dst . t   (one 1024-thread block; n is a conv dimension, <= ~20k)
 __global__ __launch_bounds__(1024) void sn_normalize_kernel(const float* __restrict__ t, int n, float eps,
@@ -28,7 +16,7 @@ __global__ __launch_bounds__(1024) void sn_normalize_kernel(const float* __restr
     __shared__ float red[16];
     float ss = 0.f;
     for (int i = threadIdx.x; i < n; i += blockDim.x) ss += t[i] * t[i];
-    ss = block_sum(ss, red);
+    ss = mg_block_sum_all<MgJoin::LeftToRight>(ss, red);
     const float denom = fmaxf(sqrtf(ss), eps);
     float dot = 0.f;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
@@ -38,7 +26,7 @@ __global__ __launch_bounds__(1024) void sn_normalize_kernel(const float* __restr
         dot += q * t[i];
     }
     if (sigma) {
-        dot = block_sum(dot, red);
+        dot = mg_block_sum_all<MgJoin::LeftToRight>(dot, red);
         if (threadIdx.x == 0) *sigma = dot;
     }
 }

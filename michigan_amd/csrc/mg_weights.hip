@@ -12,6 +12,7 @@
 //                           normalization.py:28-29: 18 layers in G, 6 in D, twice per training step each).
 // HBM-bound (weights only): K1 and K3 read every spectral-normed weight once each; no MFMA.
 #include "mg_common.h"
+#include "mg_reduce.h"
 
 namespace {
 
@@ -147,18 +148,6 @@ __global__ __launch_bounds__(256) void sn_wtu_kernel(const mg_sn_layer* __restri
     for (int j = 0; j < 4; ++j) if (c + j < L.cols) L.partial[(size_t)chunk * L.cols + c + j] = acc[j];
 }
 
-__device__ __forceinline__ float block_sum1024(float v, float* red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int i = 0; i < 16; ++i) t += red[i];
-    return t;
-}
-
 // K2: t1 = sum of the partials (fixed order), v = t1 / max(||t1||, eps)  (one 1024-thread block per layer)
 __global__ __launch_bounds__(1024) void sn_finish_v_kernel(const mg_sn_layer* __restrict__ layers, float eps)
 {
@@ -172,7 +161,7 @@ __global__ __launch_bounds__(1024) void sn_finish_v_kernel(const mg_sn_layer* __
         L.t1[c] = t;
         ss += t * t;
     }
-    ss = block_sum1024(ss, red);
+    ss = mg_block_sum_all<MgJoin::LeftToRight>(ss, red);
     const float denom = fmaxf(sqrtf(ss), eps);
     for (int c = threadIdx.x; c < L.cols; c += 1024) {
         const float q = L.t1[c] / denom;
@@ -200,8 +189,7 @@ __global__ __launch_bounds__(256) void sn_wv_kernel(const mg_sn_layer* __restric
     } else {
         for (int c = threadIdx.x & 63; c < L.cols; c += 64) acc += w[c] * L.v[c];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    acc = mg_wave_sum(acc);
     if ((threadIdx.x & 63) == 0) L.t2[r] = acc;
 }
 
@@ -214,7 +202,7 @@ __global__ __launch_bounds__(1024) void sn_finish_u_kernel(const mg_sn_layer* __
     if (power_iteration) {
         float ss = 0.f;
         for (int r = threadIdx.x; r < L.rows; r += 1024) ss += L.t2[r] * L.t2[r];
-        ss = block_sum1024(ss, red);
+        ss = mg_block_sum_all<MgJoin::LeftToRight>(ss, red);
         const float denom = fmaxf(sqrtf(ss), eps);
         for (int r = threadIdx.x; r < L.rows; r += 1024) {
             const float q = L.t2[r] / denom;
@@ -225,7 +213,7 @@ __global__ __launch_bounds__(1024) void sn_finish_u_kernel(const mg_sn_layer* __
     } else {
         for (int r = threadIdx.x; r < L.rows; r += 1024) dot += L.u[r] * L.t2[r];
     }
-    dot = block_sum1024(dot, red);
+    dot = mg_block_sum_all<MgJoin::LeftToRight>(dot, red);
     if (threadIdx.x == 0) L.sigma[0] = dot;
 }
 
