@@ -67,6 +67,34 @@ template <> struct ET<uint16_t> {
     __device__ static __forceinline__ void store1(uint16_t* p, float v) { *p = f2bf(v); }
 };
 
+// The 16-byte form: VEC = 4 fp32 / 8 bf16 consecutive channels <-> float[VEC].  raw / decode and encode are apart for a kernel that
+// keeps the loaded words in flight and decodes later (mg_feat_moments.hip); load and store are the two together.
+template <typename T> struct EV {
+    static constexpr int VEC = 16 / sizeof(T);
+    __device__ static __forceinline__ uint4 raw(const T* p) { return *reinterpret_cast<const uint4*>(p); }
+    __device__ static __forceinline__ void decode(const uint4 u, float (&v)[VEC]) {
+        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (VEC == 4) v[j] = __uint_as_float(w[j]);
+            else { v[2 * j] = __uint_as_float(w[j] << 16); v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u); }
+        }
+    }
+    __device__ static __forceinline__ uint4 encode(const float (&v)[VEC]) {
+        if constexpr (VEC == 4) return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
+        else return make_uint4(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]), f2bf2(v[6], v[7]));
+    }
+    // (fp32 goes through the float vector type, as ET<float> does: the register allocation of the norm kernels depends on it)
+    __device__ static __forceinline__ void load(const T* p, float (&v)[VEC]) {
+        if constexpr (VEC == 4) { const f32x4_t t = ET<float>::load4(p); v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
+        else decode(raw(p), v);
+    }
+    __device__ static __forceinline__ void store(T* p, const float (&v)[VEC]) {
+        if constexpr (VEC == 4) ET<float>::store4(p, f32x4_t{v[0], v[1], v[2], v[3]});
+        else *reinterpret_cast<uint4*>(p) = encode(v);
+    }
+};
+
 __device__ __forceinline__ float mg_act(float v, int act, float slope) {
     switch (act) {
         case MG_ACT_RELU:  return v > 0.f ? v : 0.f;

@@ -79,36 +79,12 @@ struct FmArgs {
     float *part, *qsum, *coef, *out;
 };
 
-// 16 bytes of channels: 4 fp32 or 8 bf16
-template <typename T> struct FV;
-template <> struct FV<float> {
-    static constexpr int VEC = 4;
-    __device__ static __forceinline__ void decode(const uint4 u, float (&v)[4]) {
-        v[0] = __uint_as_float(u.x); v[1] = __uint_as_float(u.y); v[2] = __uint_as_float(u.z); v[3] = __uint_as_float(u.w);
-    }
-    __device__ static __forceinline__ uint4 encode(const float (&v)[4]) {
-        return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
-    }
-};
-template <> struct FV<uint16_t> {
-    static constexpr int VEC = 8;
-    __device__ static __forceinline__ void decode(const uint4 u, float (&v)[8]) {
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { v[2 * j] = __uint_as_float(w[j] << 16); v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u); }
-    }
-    __device__ static __forceinline__ uint4 encode(const float (&v)[8]) {
-        return make_uint4(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]), f2bf2(v[6], v[7]));
-    }
-};
-template <typename T> __device__ __forceinline__ uint4 fm_load(const T* p) { return *reinterpret_cast<const uint4*>(p); }
-
 // MASKED: at least one mask pointer is given (a NULL one among them reads as 1).  Unmasked, sum m y = sum m^3 y = sum m^4 y: only
 // planes A1 and A4 are formed and the final kernel reads those.
 template <typename T, bool MASKED>
 __global__ __launch_bounds__(256) void feat_moment_partial_kernel(const FmArgs a)
 {
-    constexpr int VEC = FV<T>::VEC;
+    constexpr int VEC = EV<T>::VEC;
     __shared__ float red[3][256 * VEC];
     __shared__ double mred[FM_MSUMS][4];
     __shared__ float qred[4];
@@ -164,8 +140,8 @@ __global__ __launch_bounds__(256) void feat_moment_partial_kernel(const FmArgs a
     }
     float qs = 0.f;
     if (active) {
-        if (style && px != INT_MAX) FV<T>::decode(fm_load(xb + (p0 + px) * a.C), kx);
-        if (style && ps != INT_MAX) FV<T>::decode(fm_load(sb + (p0 + ps) * a.C), ks);
+        if (style && px != INT_MAX) EV<T>::load(xb + (p0 + px) * a.C, kx);
+        if (style && ps != INT_MAX) EV<T>::load(sb + (p0 + ps) * a.C, ks);
         for (int64_t pp = p0 + tr; pp < p1; pp += (int64_t)a.rows * FM_PIX) {
             uint4 rx[FM_PIX], rs[FM_PIX], rt[FM_PIX];
             float vm[FM_PIX], vs[FM_PIX], vl[FM_PIX];
@@ -176,14 +152,14 @@ __global__ __launch_bounds__(256) void feat_moment_partial_kernel(const FmArgs a
                 vm[k] = (ok && style) ? (mx ? mx[p] : 1.f) : 0.f;
                 vs[k] = (ok && style) ? (ms ? ms[p] : 1.f) : 0.f;
                 vl[k] = (ok && content) ? (ml ? ml[p] : 1.f) : 0.f;
-                if (vm[k] != 0.f || vl[k] != 0.f) rx[k] = fm_load(xb + p * a.C);
-                if (vs[k] != 0.f) rs[k] = fm_load(sb + p * a.C);
-                if (vl[k] != 0.f) rt[k] = fm_load(tb + p * a.C);
+                if (vm[k] != 0.f || vl[k] != 0.f) rx[k] = EV<T>::raw(xb + p * a.C);
+                if (vs[k] != 0.f) rs[k] = EV<T>::raw(sb + p * a.C);
+                if (vl[k] != 0.f) rt[k] = EV<T>::raw(tb + p * a.C);
             }
 #pragma unroll
             for (int k = 0; k < FM_PIX; ++k) {
                 float xv[VEC], ov[VEC];
-                if (vm[k] != 0.f || vl[k] != 0.f) FV<T>::decode(rx[k], xv);
+                if (vm[k] != 0.f || vl[k] != 0.f) EV<T>::decode(rx[k], xv);
                 if (vm[k] != 0.f) {
                     const float m = vm[k], m2 = m * m, m3 = m2 * m, m4 = m2 * m2;
 #pragma unroll
@@ -196,7 +172,7 @@ __global__ __launch_bounds__(256) void feat_moment_partial_kernel(const FmArgs a
                     }
                 }
                 if (vs[k] != 0.f) {
-                    FV<T>::decode(rs[k], ov);
+                    EV<T>::decode(rs[k], ov);
                     const float m = vs[k], m2 = m * m, m3 = m2 * m, m4 = m2 * m2;
 #pragma unroll
                     for (int j = 0; j < VEC; ++j) {
@@ -208,7 +184,7 @@ __global__ __launch_bounds__(256) void feat_moment_partial_kernel(const FmArgs a
                     }
                 }
                 if (vl[k] != 0.f) {
-                    FV<T>::decode(rt[k], ov);
+                    EV<T>::decode(rt[k], ov);
 #pragma unroll
                     for (int j = 0; j < VEC; ++j) { const float d = vl[k] * (xv[j] - ov[j]); qs += d * d; }
                 }
@@ -220,18 +196,13 @@ __global__ __launch_bounds__(256) void feat_moment_partial_kernel(const FmArgs a
     if (style) {
         float* __restrict__ dst = a.part + ((int64_t)n * a.nchunks + ck) * FM_PLANES * a.C + c;
         const bool wr = active && tr == 0;
-        auto put = [&](int slot, const float (&v)[VEC]) {
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) red[slot][tid * VEC + j] = v[j];
-        };
-        auto fold = [&](int slot, const float (&v)[VEC], int plane) {
+        auto put = [&](int slot, float (&v)[VEC]) { float* const t[1] = {v}; mg_rows_put<1, VEC>(t, red[slot]); };
+        auto fold = [&](int slot, float (&v)[VEC], int plane) {                 // the row join of mg_reduce.h, one term per LDS slot
             if (!wr) return;
+            float* const t[1] = {v};
+            mg_rows_fold<1, VEC>(t, red[slot], a.tile_cv, a.rows);
 #pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                float t = v[j];
-                for (int rr = 1; rr < a.rows; ++rr) t += red[slot][(tid + rr * a.tile_cv) * VEC + j];
-                dst[(int64_t)plane * a.C + j] = t;
-            }
+            for (int j = 0; j < VEC; ++j) dst[(int64_t)plane * a.C + j] = v[j];
         };
         const bool lds = a.rows > 1;                                      // uniform
         if (MASKED) {
@@ -371,7 +342,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void feat_moment_bwd_kernel(const FmArgs a, const float* __restrict__ g_style, const float* __restrict__ g_content,
                                                               T* __restrict__ dx)
 {
-    constexpr int VEC = FV<T>::VEC;
+    constexpr int VEC = EV<T>::VEC;
     const int tid = threadIdx.x, ct = blockIdx.y, n = blockIdx.z;
     const int tq = tid % a.tile_cv, tr = tid / a.tile_cv;
     const int cvec = ct * FM_TILE + tq;
@@ -405,8 +376,8 @@ __global__ __launch_bounds__(256) void feat_moment_bwd_kernel(const FmArgs a, co
             const bool ok = p < a.P;
             vm[k] = (ok && style) ? (mx ? mx[p] : 1.f) : 0.f;
             vl[k] = (ok && content) ? (ml ? ml[p] : 1.f) : 0.f;
-            if (vm[k] != 0.f || vl[k] != 0.f) rx[k] = fm_load(xb + p * a.C);
-            if (vl[k] != 0.f) rt[k] = fm_load(tb + p * a.C);
+            if (vm[k] != 0.f || vl[k] != 0.f) rx[k] = EV<T>::raw(xb + p * a.C);
+            if (vl[k] != 0.f) rt[k] = EV<T>::raw(tb + p * a.C);
         }
 #pragma unroll
         for (int k = 0; k < FM_PIX; ++k) {
@@ -415,19 +386,19 @@ __global__ __launch_bounds__(256) void feat_moment_bwd_kernel(const FmArgs a, co
             float xv[VEC], tv[VEC], o[VEC];
 #pragma unroll
             for (int j = 0; j < VEC; ++j) o[j] = 0.f;
-            if (vm[k] != 0.f || vl[k] != 0.f) FV<T>::decode(rx[k], xv);
+            if (vm[k] != 0.f || vl[k] != 0.f) EV<T>::decode(rx[k], xv);
             if (vm[k] != 0.f) {
                 const float m = vm[k], m3 = m * m * m;
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) o[j] = m * ca[j] + m3 * cb[j] * (m * xv[j] - mu[j]);
             }
             if (vl[k] != 0.f) {
-                FV<T>::decode(rt[k], tv);
+                EV<T>::decode(rt[k], tv);
                 const float g = gc * (vl[k] * vl[k]);
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) o[j] += g * (xv[j] - tv[j]);
             }
-            *reinterpret_cast<uint4*>(ob + p * a.C) = FV<T>::encode(o);
+            EV<T>::store(ob + p * a.C, o);
         }
     }
 }

@@ -19,7 +19,7 @@
 #include "mg_common.h"
 #include "mg_launch.h"
 #include "mg_options.h"
-#include <type_traits>
+#include "mg_reduce.h"
 
 
 namespace {
@@ -62,22 +62,6 @@ __device__ __forceinline__ size_t up_src_offset(int q, int H, int W, int C, int 
     return ((size_t)(n * (H >> 1) + (yy >> 1)) * (W >> 1) + (xx >> 1)) * C + c;
 }
 
-// a + this thread's share of column p[0] of the [nchunks][C2] partials: chunks k, k + 8, ... in fp64, fixed order.
-// Eight independent loads in flight per thread (the trip count is a runtime value: without the explicit batch the loop was a
-// chain of ~64 dependent L2 round trips, 10.6 us per launch, 99 launches per step); same summation order as the plain loop
-__device__ __forceinline__ double chunk_sum_f64(double a, const float* p, int k, int nchunks, int C2)
-{
-    for (; k + 56 < nchunks; k += 64) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = p[(size_t)(k + 8 * j) * C2];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a += (double)v[j];
-    }
-    for (; k < nchunks; k += 8) a += (double)p[(size_t)k * C2];
-    return a;
-}
-
 // sums of one channel -> mean / rstd (fp64 inside) and the optional running-statistics update of channel c: the one copy of this
 // arithmetic, so mg_channel_stats_finalize is bit-identical to mg_channel_stats + mg_norm_finalize by construction.  at() is the
 // channel's index into mean / rstd, a callable so that it is formed at the stores, where each caller had it: both kernels keep
@@ -99,86 +83,119 @@ __device__ __forceinline__ void finalize_channel(double s, double ss, double cou
     }
 }
 
-// MODE 0: plain (sum x, sum x^2).  MODE 1: norm backward (sum dxhat, sum dxhat*xhat [+ dgb]).
-template <typename T, int MODE, bool HAS_H = true>
-__global__ __launch_bounds__(MG_NTHR) void reduce_stage1(
-    const T* __restrict__ x, const T* __restrict__ dh, const T* __restrict__ h, const T* __restrict__ g1,
-    const float* __restrict__ mean, const float* __restrict__ rstd, T* __restrict__ dgb,
-    float* __restrict__ partial, int64_t P, int C, int tpr, int rpb, int64_t chunk, int act, float slope,
-    int up = 0, int H = 0, int W = 0)
+// dxhat = (dh * act'(h)) * (1 + gamma) of one element, and its first product dpre, which d[gamma | beta] take.  The quad kernels
+// go through mg_act_grad_from_out (any activation, h = 1 where there is none); the channel-resident ones know NONE / RELU / LRELU
+// as neg = mg_neg_slope(act, slope), and a missing h or g1 is a factor 1 that is not multiplied
+struct DxHat { float dpre, dxh; };
+__device__ __forceinline__ DxHat dxhat_quad(float dv, float hv, float gv, int act, float slope)
+{
+    const float dpre = dv * mg_act_grad_from_out(hv, act, slope);
+    return {dpre, dpre * gv};
+}
+__device__ __forceinline__ DxHat dxhat_vec(float dv, float hv, float gv, float neg, bool has_h, bool has_g1)
+{
+    const float dpre = has_h ? dv * mg_act_factor(hv, neg) : dv;
+    return {dpre, has_g1 ? dpre * gv : dpre};
+}
+
+// the end of every stage-1 kernel: the row join of mg_reduce.h, then row 0 stores its W channels from c of partial[g][chunk][2][C]
+// (grid (chunks, G))
+template <int W>
+__device__ __forceinline__ void join_to_partial(float (&s)[W], float (&ss)[W], float* red, int cv, int rows, bool row0, float* __restrict__ partial, int C, int c)
+{
+    float* const terms[2] = {s, ss};
+    mg_row_join<2, W>(terms, red, cv, rows, row0);
+    if (row0) {
+        float* dst = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * C + c;
+#pragma unroll
+        for (int j = 0; j < W; ++j) { dst[j] = s[j]; dst[C + j] = ss[j]; }
+    }
+}
+
+// quad thread (tq, tr) of tpr x rpb and the pixels [p0, p1) of the workgroup's chunk
+struct QuadChunk { int tq, tr; bool active; int64_t p0, p1; };
+__device__ __forceinline__ QuadChunk quad_chunk(int64_t P, int tpr, int rpb, int64_t chunk)
+{
+    const int tid = threadIdx.x;
+    const int64_t p0 = (int64_t)blockIdx.x * chunk;
+    return {tid % tpr, tid / tpr, tid < tpr * rpb, p0, (p0 + chunk < P) ? p0 + chunk : P};
+}
+
+// stage 1 of the plain statistics (sum x, sum x^2) for any C % 4 == 0
+template <typename T>
+__global__ __launch_bounds__(MG_NTHR) void stats_stage1_quad(const T* __restrict__ x, float* __restrict__ partial, int64_t P, int C,
+                                                             int tpr, int rpb, int64_t chunk, int shift)
 {
     __shared__ float red[MG_NTHR * 8];
-    const int tid = threadIdx.x;
-    const int g = blockIdx.y, ck = blockIdx.x, nchunks = gridDim.x;
-    const int c4 = C / 4;
-    const bool active = tid < tpr * rpb;
-    const int tq = tid % tpr, tr = tid / tpr;
+    const int g = blockIdx.y, c4 = C / 4;
+    const auto [tq, tr, active, p0, p1] = quad_chunk(P, tpr, rpb, chunk);
+    for (int qd0 = 0; qd0 < c4; qd0 += tpr) {         // uniform trip count (one trip unless C > 1024)
+        const int qd = qd0 + tq;
+        const bool qv = active && qd < c4;
+        const int c = (qd < c4 ? qd : 0) * 4;
+        float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
+        f32x4_t kv = {0.f, 0.f, 0.f, 0.f};
+        if (shift) kv = ET<T>::load4(x + (size_t)g * P * C + c);     // pivot = the group's first pixel
+        if (qv) {
+            for (int64_t p = p0 + tr; p < p1; p += rpb) {
+                const f32x4_t xv = ET<T>::load4(x + ((size_t)g * P + p) * C + c);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { const float t = xv[j] - kv[j]; s[j] += t; ss[j] += t * t; }
+            }
+        }
+        join_to_partial(s, ss, red, tpr, rpb, qv && tr == 0, partial, C, c);
+        __syncthreads();                                 // red is free for the next channel trip
+    }
+}
+
+// stage 1 of the norm backward reduction (sum dxhat, sum dxhat * xhat, optional d[gamma|beta] output) for any C % 4 == 0 and any
+// activation; `up`: x is the half-resolution source of a nearest 2x upsample (G == 1)
+template <typename T, bool HAS_H>
+__global__ __launch_bounds__(MG_NTHR) void bwd_stage1_quad(
+    const T* __restrict__ x, const T* __restrict__ dh, const T* __restrict__ h, const T* __restrict__ g1,
+    const float* __restrict__ mean, const float* __restrict__ rstd, T* __restrict__ dgb,
+    float* __restrict__ partial, int64_t P, int C, int tpr, int rpb, int64_t chunk, int act, float slope, int up, int H, int W)
+{
+    __shared__ float red[MG_NTHR * 8];
+    const int g = blockIdx.y, c4 = C / 4;
+    const auto [tq, tr, active, p0, p1] = quad_chunk(P, tpr, rpb, chunk);
     const int Cr2 = 2 * ((C + 31) / 32) * 32;
-
-    const int64_t p0 = (int64_t)ck * chunk;
-    const int64_t p1 = (p0 + chunk < P) ? p0 + chunk : P;
-
     for (int qd0 = 0; qd0 < c4; qd0 += tpr) {         // uniform trip count (one trip unless C > 1024)
         const int qd = qd0 + tq;
         const bool qv = active && qd < c4;
         const int c = (qd < c4 ? qd : 0) * 4;
         float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
         f32x4_t mu, rs;
-        f32x4_t kv = {0.f, 0.f, 0.f, 0.f};
-        if (MODE == 0 && up) kv = ET<T>::load4(x + (size_t)g * P * C + c);     // MODE 0: `up` carries the shift flag -- pivot = the group's first pixel
-        if (MODE == 1) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { mu[j] = mean[(size_t)g * C + c + j]; rs[j] = rstd[(size_t)g * C + c + j]; }
-        }
+        for (int j = 0; j < 4; ++j) { mu[j] = mean[(size_t)g * C + c + j]; rs[j] = rstd[(size_t)g * C + c + j]; }
         if (qv) {
             for (int64_t p = p0 + tr; p < p1; p += rpb) {
                 const size_t o = ((size_t)g * P + p) * C + c;
                 size_t ox = o;
-                if (MODE == 1 && up) ox = up_src_offset((int)p, H, W, C, c);      // x is the half-resolution source of a nearest 2x upsample (G == 1)
+                if (up) ox = up_src_offset((int)p, H, W, C, c);
                 const f32x4_t xv = ET<T>::load4(x + ox);
-                if (MODE == 0) {
+                const f32x4_t dv = ET<T>::load4(dh + o);
+                f32x4_t hv = {1.f, 1.f, 1.f, 1.f};              // h only matters through the sign of the activation's output
+                if constexpr (HAS_H) hv = ET<T>::load4(h + o);
+                f32x4_t gv = {1.f, 1.f, 1.f, 1.f};
+                if (g1) gv = ET<T>::load4(g1 + o);
+                f32x4_t dgam, dbet;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) { const float t = xv[j] - kv[j]; s[j] += t; ss[j] += t * t; }
-                } else {
-                    const f32x4_t dv = ET<T>::load4(dh + o);
-                    f32x4_t hv = {1.f, 1.f, 1.f, 1.f};              // h only matters through the sign of the activation's output
-                    if constexpr (HAS_H) hv = ET<T>::load4(h + o);
-                    f32x4_t gv = {1.f, 1.f, 1.f, 1.f};
-                    if (g1) gv = ET<T>::load4(g1 + o);
-                    f32x4_t dgam, dbet;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float dpre = dv[j] * mg_act_grad_from_out(hv[j], act, slope);
-                        const float xh = (xv[j] - mu[j]) * rs[j];
-                        const float dxh = dpre * gv[j];
-                        s[j] += dxh; ss[j] += dxh * xh;
-                        dgam[j] = dpre * xh; dbet[j] = dpre;
-                    }
-                    if (dgb) {
-                        const size_t ob = ((size_t)g * P + p) * Cr2 + (size_t)(c >> 5) * 64 + (c & 31);
-                        ET<T>::store4(dgb + ob, dgam);
-                        ET<T>::store4(dgb + ob + 32, dbet);
-                    }
+                for (int j = 0; j < 4; ++j) {
+                    const DxHat d = dxhat_quad(dv[j], hv[j], gv[j], act, slope);
+                    const float xh = (xv[j] - mu[j]) * rs[j];
+                    s[j] += d.dxh; ss[j] += d.dxh * xh;
+                    dgam[j] = d.dpre * xh; dbet[j] = d.dpre;
+                }
+                if (dgb) {
+                    const size_t ob = ((size_t)g * P + p) * Cr2 + (size_t)(c >> 5) * 64 + (c & 31);
+                    ET<T>::store4(dgb + ob, dgam);
+                    ET<T>::store4(dgb + ob + 32, dbet);
                 }
             }
         }
-        // cross-row reduce through LDS (rows tr = 0..rpb-1 share quad tq)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { red[tid * 8 + j] = s[j]; red[tid * 8 + 4 + j] = ss[j]; }
-        __syncthreads();
-        if (qv && tr == 0) {
-            float a[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] = red[tid * 8 + j];
-            for (int r = 1; r < rpb; ++r) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) a[j] += red[(tid + r * tpr) * 8 + j];
-            }
-            float* dst = partial + ((size_t)g * nchunks + ck) * 2 * C;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { dst[c + j] = a[j]; dst[C + c + j] = a[4 + j]; }
-        }
-        __syncthreads();
+        join_to_partial(s, ss, red, tpr, rpb, qv && tr == 0, partial, C, c);
+        __syncthreads();                                 // red is free for the next channel trip
     }
 }
 
@@ -191,14 +208,9 @@ __global__ __launch_bounds__(256) void reduce_stage2(const float* __restrict__ p
     const int i = blockIdx.x * 32 + cl;
     const int g = blockIdx.y;
     double a = 0.0;
-    if (i < C2) a = chunk_sum_f64(a, partial + (size_t)g * nchunks * C2 + i, kk, nchunks, C2);
-    red[threadIdx.x] = a;
-    __syncthreads();
-    if (kk == 0 && i < C2) {
-#pragma unroll
-        for (int r = 1; r < 8; ++r) a += red[r * 32 + cl];
-        sums[(size_t)g * C2 + i] = (float)a;
-    }
+    if (i < C2) a = mg_chunk_sum_f64(a, partial + (size_t)g * nchunks * C2 + i, kk, nchunks, C2);
+    a = mg_chunk_rows_join(a, red);
+    if (kk == 0 && i < C2) sums[(size_t)g * C2 + i] = (float)a;
 }
 
 template <typename T>
@@ -249,7 +261,7 @@ __global__ void norm_bwd_apply_kernel(const T* __restrict__ dh, const T* __restr
         for (int j = 0; j < 4; ++j) {
             const float r = rstd[sc + j];
             const float xh = (xv[j] - mean[sc + j]) * r;
-            const float dxh = dv[j] * mg_act_grad_from_out(hv[j], act, slope) * gv[j];
+            const float dxh = dxhat_quad(dv[j], hv[j], gv[j], act, slope).dxh;
             o[j] = r * (dxh - s1[ss + j] * sscale - xh * (s2[ss + j] * sscale));
         }
         ET<T>::store4(dx + i * 4, o);
@@ -263,49 +275,31 @@ __global__ void norm_bwd_apply_kernel(const T* __restrict__ dh, const T* __restr
 // are loaded once, the pixel loop has no integer division, every access is a full 16-byte vector and PIX
 // independent pixels are in flight per thread.  The quad kernels above (8-byte accesses, div/mod and 16 scalar
 // parameter loads per quad) ran at 2.0-2.5 TB/s on [8,512,512,128] bf16; these run at 4-5 TB/s (tools/bench_pointwise.py).
-template <typename T> struct VT;
-template <> struct VT<float> {
-    static constexpr int VEC = 4;
-    __device__ static __forceinline__ void load(const float* p, float (&v)[4]) {
-        const f32x4_t t = *reinterpret_cast<const f32x4_t*>(p);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = t[j];
-    }
-    __device__ static __forceinline__ void store(float* p, const float (&v)[4]) {
-        f32x4_t t;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) t[j] = v[j];
-        *reinterpret_cast<f32x4_t*>(p) = t;
-    }
-};
-template <> struct VT<uint16_t> {
-    static constexpr int VEC = 8;
-    __device__ static __forceinline__ void load(const uint16_t* p, float (&v)[8]) {
-        const uint4 u = *reinterpret_cast<const uint4*>(p);
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { v[2 * j] = __uint_as_float(w[j] << 16); v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u); }
-    }
-    __device__ static __forceinline__ void store(uint16_t* p, const float (&v)[8]) {
-        uint4 u;
-        u.x = f2bf2(v[0], v[1]); u.y = f2bf2(v[2], v[3]); u.z = f2bf2(v[4], v[5]); u.w = f2bf2(v[6], v[7]);
-        *reinterpret_cast<uint4*>(p) = u;
-    }
-};
-
-// f(std::true_type) or f(std::false_type): a runtime flag as a template argument (the true branch first, like mg_by_dtype)
-template <typename F> static inline void by_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
-
 template <typename T> static inline bool vec_geom_ok(int C)
 {
-    constexpr int VEC = VT<T>::VEC;
+    constexpr int VEC = EV<T>::VEC;
     if (C % VEC) return false;
     const int cv = C / VEC;
     return cv <= MG_NTHR && MG_NTHR % cv == 0;
 }
+// this (T, C, act) takes the channel-resident kernel: TANH stays on the quad kernels
+template <typename T> static inline bool takes_vec(int C, int act) { return act != MG_ACT_TANH && vec_geom_ok<T>(C); }
+template <typename T> static inline int vec_rows(int C) { return MG_NTHR / (C / EV<T>::VEC); }
 
-// derivative factor of NONE / RELU / LRELU through the output: y > 0 ? 1 : neg
-__device__ __forceinline__ float act_factor(float y, float neg) { return y > 0.f ? 1.f : neg; }
+// channel-resident thread (tq, tr) of cv x rows: channels c .. c + VEC - 1 for the whole launch
+struct ChanThread { int cv, rows, tq, tr, c; };
+template <int VEC> __device__ __forceinline__ ChanThread chan_thread(int C)
+{
+    const int cv = C / VEC, tq = threadIdx.x % cv;
+    const int tr = threadIdx.x / cv;
+    return {cv, MG_NTHR / cv, tq, tr, tq * VEC};
+}
+// its channels' mean / rstd (of one group: the caller offsets the pointers) into registers
+template <int VEC> __device__ __forceinline__ void chan_stats(const float* __restrict__ mean, const float* __restrict__ rstd, float (&m)[VEC], float (&r)[VEC])
+{
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) { m[j] = mean[j]; r[j] = rstd[j]; }
+}
 
 template <typename T, int PIX>
 __global__ __launch_bounds__(MG_NTHR) void norm_bwd_apply_vec(const T* __restrict__ dh, const T* __restrict__ h, const T* __restrict__ x,
@@ -313,15 +307,15 @@ __global__ __launch_bounds__(MG_NTHR) void norm_bwd_apply_vec(const T* __restric
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          const float* __restrict__ s1, const float* __restrict__ s2, int sgs, float sscale, float neg)
 {
-    constexpr int VEC = VT<T>::VEC;
-    const int cv = C / VEC, rows = MG_NTHR / cv;
-    const int tq = threadIdx.x % cv, tr = threadIdx.x / cv;
-    const int g = blockIdx.y, c = tq * VEC;
+    constexpr int VEC = EV<T>::VEC;
+    const auto [cv, rows, tq, tr, c] = chan_thread<VEC>(C);
+    const int g = blockIdx.y;
     float m[VEC], r[VEC], c1[VEC], c2[VEC];
+    chan_stats(mean + (size_t)g * C + c, rstd + (size_t)g * C + c, m, r);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-        const size_t i = (size_t)g * C + c + j, k = (size_t)g * sgs + c + j;
-        m[j] = mean[i]; r[j] = rstd[i]; c1[j] = r[j] * (s1[k] * sscale); c2[j] = r[j] * r[j] * (s2[k] * sscale);
+        const size_t k = (size_t)g * sgs + c + j;
+        c1[j] = r[j] * (s1[k] * sscale); c2[j] = r[j] * r[j] * (s2[k] * sscale);
     }
     const size_t base = (size_t)g * P * C + c;
     const int64_t step = (int64_t)gridDim.x * rows;
@@ -332,9 +326,9 @@ __global__ __launch_bounds__(MG_NTHR) void norm_bwd_apply_vec(const T* __restric
             const int64_t p = p0 + k * step;
             if (p < P) {
                 const size_t o = base + (size_t)p * C;
-                VT<T>::load(dh + o, dv[k]); VT<T>::load(x + o, xv[k]);
-                if (h) VT<T>::load(h + o, hv[k]);
-                if (g1) VT<T>::load(g1 + o, gv[k]);
+                EV<T>::load(dh + o, dv[k]); EV<T>::load(x + o, xv[k]);
+                if (h) EV<T>::load(h + o, hv[k]);
+                if (g1) EV<T>::load(g1 + o, gv[k]);
             }
         }
 #pragma unroll
@@ -344,11 +338,10 @@ __global__ __launch_bounds__(MG_NTHR) void norm_bwd_apply_vec(const T* __restric
                 float o4[VEC];
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
-                    float dxh = h ? dv[k][j] * act_factor(hv[k][j], neg) : dv[k][j];
-                    if (g1) dxh *= gv[k][j];
+                    const float dxh = dxhat_vec(dv[k][j], hv[k][j], gv[k][j], neg, h != nullptr, g1 != nullptr).dxh;
                     o4[j] = r[j] * dxh - c1[j] - c2[j] * (xv[k][j] - m[j]);
                 }
-                VT<T>::store(dx + base + (size_t)p * C, o4);
+                EV<T>::store(dx + base + (size_t)p * C, o4);
             }
         }
     }
@@ -359,13 +352,11 @@ __global__ __launch_bounds__(MG_NTHR) void norm_act_fwd_vec(const T* __restrict_
                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
                                                        float neg, bool relu, const T* __restrict__ resid)
 {
-    constexpr int VEC = VT<T>::VEC;
-    const int cv = C / VEC, rows = MG_NTHR / cv;
-    const int tq = threadIdx.x % cv, tr = threadIdx.x / cv;
-    const int g = blockIdx.y, c = tq * VEC;
+    constexpr int VEC = EV<T>::VEC;
+    const auto [cv, rows, tq, tr, c] = chan_thread<VEC>(C);
+    const int g = blockIdx.y;
     float m[VEC], r[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) { m[j] = mean[(size_t)g * C + c + j]; r[j] = rstd[(size_t)g * C + c + j]; }
+    chan_stats(mean + (size_t)g * C + c, rstd + (size_t)g * C + c, m, r);
     const size_t base = (size_t)g * P * C + c;
     const int64_t step = (int64_t)gridDim.x * rows;
     for (int64_t p0 = (int64_t)blockIdx.x * rows + tr; p0 < P; p0 += step * PIX) {
@@ -373,7 +364,7 @@ __global__ __launch_bounds__(MG_NTHR) void norm_act_fwd_vec(const T* __restrict_
 #pragma unroll
         for (int k = 0; k < PIX; ++k) {
             const int64_t p = p0 + k * step;
-            if (p < P) { VT<T>::load(x + base + (size_t)p * C, xv[k]); if (resid) VT<T>::load(resid + base + (size_t)p * C, rv[k]); }
+            if (p < P) { EV<T>::load(x + base + (size_t)p * C, xv[k]); if (resid) EV<T>::load(resid + base + (size_t)p * C, rv[k]); }
         }
 #pragma unroll
         for (int k = 0; k < PIX; ++k) {
@@ -387,28 +378,27 @@ __global__ __launch_bounds__(MG_NTHR) void norm_act_fwd_vec(const T* __restrict_
                     o4[j] = relu ? fmaxf(v, 0.f) : t;
                     if (resid) o4[j] += rv[k][j];
                 }
-                VT<T>::store(y + base + (size_t)p * C, o4);
+                EV<T>::store(y + base + (size_t)p * C, o4);
             }
         }
     }
 }
 
-// stage 1 of the plain statistics (sum x, sum x^2) with the same chunking / partial layout as reduce_stage1<T, 0>
+// stage 1 of the plain statistics (sum x, sum x^2) with the same chunking / partial layout as stats_stage1_quad
 template <typename T, int PIX>
 __global__ __launch_bounds__(MG_NTHR) void stats_stage1_vec(const T* __restrict__ x, float* __restrict__ partial, int64_t P, int C, int64_t chunk, int shift)
 {
-    constexpr int VEC = VT<T>::VEC;
+    constexpr int VEC = EV<T>::VEC;
     __shared__ float red[MG_NTHR * 2 * VEC];
-    const int cv = C / VEC, rows = MG_NTHR / cv;
-    const int tq = threadIdx.x % cv, tr = threadIdx.x / cv;
-    const int g = blockIdx.y, ck = blockIdx.x, nchunks = gridDim.x, c = tq * VEC;
-    const int64_t p0 = (int64_t)ck * chunk;
+    const auto [cv, rows, tq, tr, c] = chan_thread<VEC>(C);
+    const int g = blockIdx.y;
+    const int64_t p0 = (int64_t)blockIdx.x * chunk;
     const int64_t p1 = (p0 + chunk < P) ? p0 + chunk : P;
     float s[VEC], ss[VEC], kv[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) { s[j] = 0.f; ss[j] = 0.f; }
     const size_t base = (size_t)g * P * C + c;
-    if (shift) VT<T>::load(x + base, kv);                                // pivot of the shifted sums: the group's first pixel
+    if (shift) EV<T>::load(x + base, kv);                                // pivot of the shifted sums: the group's first pixel
     else {
 #pragma unroll
         for (int j = 0; j < VEC; ++j) kv[j] = 0.f;
@@ -418,7 +408,7 @@ __global__ __launch_bounds__(MG_NTHR) void stats_stage1_vec(const T* __restrict_
 #pragma unroll
         for (int k = 0; k < PIX; ++k) {
             const int64_t p = pp + (int64_t)k * rows;
-            if (p < p1) VT<T>::load(x + base + (size_t)p * C, xv[k]);
+            if (p < p1) EV<T>::load(x + base + (size_t)p * C, xv[k]);
             else {
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) xv[k][j] = kv[j];           // contributes (k - k) = 0
@@ -429,25 +419,11 @@ __global__ __launch_bounds__(MG_NTHR) void stats_stage1_vec(const T* __restrict_
 #pragma unroll
             for (int j = 0; j < VEC; ++j) { const float t = xv[k][j] - kv[j]; s[j] += t; ss[j] += t * t; }
     }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) { red[threadIdx.x * 2 * VEC + j] = s[j]; red[threadIdx.x * 2 * VEC + VEC + j] = ss[j]; }
-    __syncthreads();
-    if (tr == 0) {
-        float* dst = partial + ((size_t)g * nchunks + ck) * 2 * C;
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            float a = s[j], b = ss[j];
-            for (int rr = 1; rr < rows; ++rr) {                              // fixed order: deterministic
-                a += red[(threadIdx.x + rr * cv) * 2 * VEC + j];
-                b += red[(threadIdx.x + rr * cv) * 2 * VEC + VEC + j];
-            }
-            dst[c + j] = a; dst[C + c + j] = b;
-        }
-    }
+    join_to_partial(s, ss, red, cv, rows, tr == 0, partial, C, c);
 }
 
 // stage 1 of the norm backward reduction (sum dxhat, sum dxhat * xhat, optional d[gamma|beta] output), 16-byte variant of
-// reduce_stage1<T, 1>: a thread keeps VEC channels (mean / rstd loaded once), PIX pixels in flight, every access a full 16-byte
+// bwd_stage1_quad: a thread keeps VEC channels (mean / rstd loaded once), PIX pixels in flight, every access a full 16-byte
 // vector -- the quad kernel moved its four input streams in 8-byte pieces at 4.4 TB/s and was the largest non-MFMA kernel of the step.
 // Same chunking and partial layout; `act` is NONE / RELU / LRELU only (neg = 1 / 0 / slope), TANH stays on the quad kernel.
 template <typename T, int PIX, bool HAS_H, bool UP>
@@ -455,17 +431,17 @@ __global__ __launch_bounds__(MG_NTHR) void bwd_stage1_vec(const T* __restrict__ 
                                                      const float* __restrict__ mean, const float* __restrict__ rstd, T* __restrict__ dgb,
                                                      float* __restrict__ partial, int64_t P, int C, int64_t chunk, float neg, int H, int W)
 {
-    constexpr int VEC = VT<T>::VEC;
+    constexpr int VEC = EV<T>::VEC;
     __shared__ float red[MG_NTHR * 2 * VEC];
-    const int cv = C / VEC, rows = MG_NTHR / cv;
-    const int tq = threadIdx.x % cv, tr = threadIdx.x / cv;
-    const int g = blockIdx.y, ck = blockIdx.x, nchunks = gridDim.x, c = tq * VEC;
+    const auto [cv, rows, tq, tr, c] = chan_thread<VEC>(C);
+    const int g = blockIdx.y;
     const int Cr2 = 2 * ((C + 31) / 32) * 32;
-    const int64_t p0 = (int64_t)ck * chunk;
+    const int64_t p0 = (int64_t)blockIdx.x * chunk;
     const int64_t p1 = (p0 + chunk < P) ? p0 + chunk : P;
     float mu[VEC], rs[VEC], s[VEC], ss[VEC];
+    chan_stats(mean + (size_t)g * C + c, rstd + (size_t)g * C + c, mu, rs);
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) { mu[j] = mean[(size_t)g * C + c + j]; rs[j] = rstd[(size_t)g * C + c + j]; s[j] = 0.f; ss[j] = 0.f; }
+    for (int j = 0; j < VEC; ++j) { s[j] = 0.f; ss[j] = 0.f; }
     const size_t base = (size_t)g * P * C + c;
     const size_t gbase = (size_t)g * P * Cr2 + (size_t)(c >> 5) * 64 + (c & 31);
     for (int64_t pp = p0 + tr; pp < p1; pp += (int64_t)rows * PIX) {
@@ -476,10 +452,10 @@ __global__ __launch_bounds__(MG_NTHR) void bwd_stage1_vec(const T* __restrict__ 
             if (p < p1) {
                 size_t ox = base + (size_t)p * C;
                 if (UP) ox = up_src_offset((int)p, H, W, C, c);       // x is the half-resolution source of a nearest 2x upsample (G == 1)
-                VT<T>::load(x + ox, xv[k]);
-                VT<T>::load(dh + base + (size_t)p * C, dv[k]);
-                if (HAS_H) VT<T>::load(h + base + (size_t)p * C, hv[k]);
-                if (g1) VT<T>::load(g1 + base + (size_t)p * C, gv[k]);
+                EV<T>::load(x + ox, xv[k]);
+                EV<T>::load(dh + base + (size_t)p * C, dv[k]);
+                if (HAS_H) EV<T>::load(h + base + (size_t)p * C, hv[k]);
+                if (g1) EV<T>::load(g1 + base + (size_t)p * C, gv[k]);
             }
         }
 #pragma unroll
@@ -489,34 +465,19 @@ __global__ __launch_bounds__(MG_NTHR) void bwd_stage1_vec(const T* __restrict__ 
                 float dgam[VEC], dbet[VEC];
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
-                    const float dpre = HAS_H ? dv[k][j] * act_factor(hv[k][j], neg) : dv[k][j];
+                    const DxHat d = dxhat_vec(dv[k][j], hv[k][j], gv[k][j], neg, HAS_H, g1 != nullptr);
                     const float xh = (xv[k][j] - mu[j]) * rs[j];
-                    const float dxh = g1 ? dpre * gv[k][j] : dpre;
-                    s[j] += dxh; ss[j] += dxh * xh;
-                    dgam[j] = dpre * xh; dbet[j] = dpre;
+                    s[j] += d.dxh; ss[j] += d.dxh * xh;
+                    dgam[j] = d.dpre * xh; dbet[j] = d.dpre;
                 }
                 if (dgb) {
-                    VT<T>::store(dgb + gbase + (size_t)p * Cr2, dgam);
-                    VT<T>::store(dgb + gbase + (size_t)p * Cr2 + 32, dbet);
+                    EV<T>::store(dgb + gbase + (size_t)p * Cr2, dgam);
+                    EV<T>::store(dgb + gbase + (size_t)p * Cr2 + 32, dbet);
                 }
             }
         }
     }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) { red[threadIdx.x * 2 * VEC + j] = s[j]; red[threadIdx.x * 2 * VEC + VEC + j] = ss[j]; }
-    __syncthreads();
-    if (tr == 0) {
-        float* dst = partial + ((size_t)g * nchunks + ck) * 2 * C;
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            float a = s[j], b = ss[j];
-            for (int rr = 1; rr < rows; ++rr) {                              // fixed order: deterministic
-                a += red[(threadIdx.x + rr * cv) * 2 * VEC + j];
-                b += red[(threadIdx.x + rr * cv) * 2 * VEC + VEC + j];
-            }
-            dst[c + j] = a; dst[C + c + j] = b;
-        }
-    }
+    join_to_partial(s, ss, red, cv, rows, tr == 0, partial, C, c);
 }
 
 // sums[g][2][C] (+ element count) -> mean / rstd (fp64 inside), optional running-statistics update (G == 1):
@@ -541,18 +502,17 @@ __global__ void norm_finalize_kernel(const double* __restrict__ sums, int G, int
 template <typename T, int NB, bool UP>
 __global__ __launch_bounds__(MG_NTHR) void norm_bwd_apply2_vec(const mg_norm_apply2_desc d, float neg0, float neg1)
 {
-    constexpr int VEC = VT<T>::VEC;
-    const int C = d.C, cv = C / VEC, rows = MG_NTHR / cv;
-    const int tq = threadIdx.x % cv, tr = threadIdx.x / cv;
-    const int c = tq * VEC;
+    constexpr int VEC = EV<T>::VEC;
+    const int C = d.C;
+    const auto [cv, rows, tq, tr, c] = chan_thread<VEC>(C);
     const T* dh0 = (const T*)d.dh[0]; const T* h0 = (const T*)d.h[0]; const T* g0 = (const T*)d.g1[0];
     const T* dh1 = (const T*)d.dh[1]; const T* h1 = (const T*)d.h[1]; const T* g1 = (const T*)d.g1[1];
     const T* x = (const T*)d.x; T* dx = (T*)d.dx;
     constexpr int Q = UP ? 4 : 1;
     float m[VEC], r[VEC], k1[VEC], k2[VEC];
+    chan_stats(d.mean + c, d.rstd + c, m, r);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-        m[j] = d.mean[c + j]; r[j] = d.rstd[c + j];
         float s1 = d.sums[0][c + j], s2 = d.sums[0][C + c + j];
         if (NB == 2) { s1 += d.sums[1][c + j]; s2 += d.sums[1][C + c + j]; }
         k1[j] = (float)Q * r[j] * s1 * d.inv_count;
@@ -570,38 +530,30 @@ __global__ __launch_bounds__(MG_NTHR) void norm_bwd_apply2_vec(const mg_norm_app
             pf[0] = base; if (Q > 1) { pf[1 % Q] = base + 1; pf[2 % Q] = base + W; pf[3 % Q] = base + W + 1; }
         } else pf[0] = po;
         float xv[VEC], acc[VEC];
-        VT<T>::load(x + (size_t)po * C + c, xv);
+        EV<T>::load(x + (size_t)po * C + c, xv);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
             const size_t o = (size_t)pf[q] * C + c;
             float dv[VEC], hv[VEC], gv[VEC];
-            VT<T>::load(dh0 + o, dv);
-            if (h0) VT<T>::load(h0 + o, hv);
-            if (g0) VT<T>::load(g0 + o, gv);
+            EV<T>::load(dh0 + o, dv);
+            if (h0) EV<T>::load(h0 + o, hv);
+            if (g0) EV<T>::load(g0 + o, gv);
 #pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                float t = h0 ? dv[j] * act_factor(hv[j], neg0) : dv[j];
-                if (g0) t *= gv[j];
-                acc[j] += t;
-            }
+            for (int j = 0; j < VEC; ++j) acc[j] += dxhat_vec(dv[j], hv[j], gv[j], neg0, h0 != nullptr, g0 != nullptr).dxh;
             if (NB == 2) {
-                VT<T>::load(dh1 + o, dv);
-                if (h1) VT<T>::load(h1 + o, hv);
-                if (g1) VT<T>::load(g1 + o, gv);
+                EV<T>::load(dh1 + o, dv);
+                if (h1) EV<T>::load(h1 + o, hv);
+                if (g1) EV<T>::load(g1 + o, gv);
 #pragma unroll
-                for (int j = 0; j < VEC; ++j) {
-                    float t = h1 ? dv[j] * act_factor(hv[j], neg1) : dv[j];
-                    if (g1) t *= gv[j];
-                    acc[j] += t;
-                }
+                for (int j = 0; j < VEC; ++j) acc[j] += dxhat_vec(dv[j], hv[j], gv[j], neg1, h1 != nullptr, g1 != nullptr).dxh;
             }
         }
         float o4[VEC];
 #pragma unroll
         for (int j = 0; j < VEC; ++j) o4[j] = r[j] * acc[j] - k1[j] - k2[j] * (xv[j] - m[j]);
-        VT<T>::store(dx + (size_t)po * C + c, o4);
+        EV<T>::store(dx + (size_t)po * C + c, o4);
     }
 }
 
@@ -624,14 +576,9 @@ __global__ __launch_bounds__(256) void stats_stage2(const float* __restrict__ pa
     const int C2 = 2 * C;
     const int i = (cl >> 4) * C + c;                            // column of the [sum | sum of squares] vector
     double a = 0.0;
-    if (c < C) a = chunk_sum_f64(a, partial + (size_t)g * nchunks * C2 + i, kk, nchunks, C2);
-    red[threadIdx.x] = a;
-    __syncthreads();
-    if (kk == 0) {
-#pragma unroll
-        for (int r = 1; r < 8; ++r) a += red[r * 32 + cl];
-        fin[cl] = a;
-    }
+    if (c < C) a = mg_chunk_sum_f64(a, partial + (size_t)g * nchunks * C2 + i, kk, nchunks, C2);
+    a = mg_chunk_rows_join(a, red);
+    if (kk == 0) fin[cl] = a;
     __syncthreads();
     if (threadIdx.x < 16 && c < C) {
         const double kv = shift ? (double)ET<T>::load1(x + (size_t)g * P * C + c) : 0.0;
@@ -654,8 +601,7 @@ int run_stats(const void* x, int G, int64_t P, int C, int shift, double* sums, v
     if (vec_geom_ok<T>(C))
         hipLaunchKernelGGL((stats_stage1_vec<T, 4>), grid, dim3(MG_NTHR), 0, st, (const T*)x, (float*)partial, P, C, sg.chunk, shift);
     else
-        hipLaunchKernelGGL((reduce_stage1<T, 0, true>), grid, dim3(MG_NTHR), 0, st, (const T*)x, (const T*)nullptr, (const T*)nullptr, (const T*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, (T*)nullptr, (float*)partial, P, C, sg.tpr, sg.rpb, sg.chunk, 0, 0.f, shift, 0, 0);
+        hipLaunchKernelGGL(stats_stage1_quad<T>, grid, dim3(MG_NTHR), 0, st, (const T*)x, (float*)partial, P, C, sg.tpr, sg.rpb, sg.chunk, shift);
     MG_CHECK_LAUNCH("channel statistics (stage 1)");
     hipLaunchKernelGGL((stats_stage2<T, FIN>), dim3((C + 15) / 16, G), dim3(256), 0, st, (const float*)partial, (const T*)x, P, sums, sg.nchunks, C, shift,
                        sum_scale, count, eps, momentum, running_mean, running_var, mean, rstd);
@@ -668,25 +614,20 @@ int run_stats(const void* x, int G, int64_t P, int C, int shift, double* sums, v
 template <typename T>
 int run_reduce(const void* x, const void* dh, const void* h, const void* g1, const float* mean, const float* rstd,
                void* dgb, int G, int64_t P, int C, float* sums, void* partial, int act, float slope, hipStream_t st,
-               int up = 0, int H = 0, int W = 0)
+               int up, int H, int W)
 {
     const StatGeom sg = stat_geom(G, P, C);
     dim3 grid(sg.nchunks, G);
-    if (mg_opt(MG_OPT_NORM_BWD_VEC) && vec_geom_ok<T>(C) && act != MG_ACT_TANH) {
+    if (mg_opt(MG_OPT_NORM_BWD_VEC) && takes_vec<T>(C, act)) {
         // (d[gamma|beta] rows are 32-channel blocks; a thread's VEC channels start at a multiple of VEC and stay inside one block)
         const float neg = mg_neg_slope(act, slope);
-        by_bool(h != nullptr && act != MG_ACT_NONE, [&](auto hh) { by_bool(up != 0, [&](auto upf) {
+        mg_by_bool(h != nullptr && act != MG_ACT_NONE, [&](auto hh) { mg_by_bool(up != 0, [&](auto upf) {
             hipLaunchKernelGGL((bwd_stage1_vec<T, 2, hh.value, upf.value>), grid, dim3(MG_NTHR), 0, st, (const T*)x, (const T*)dh, (const T*)h,
                                (const T*)g1, mean, rstd, (T*)dgb, (float*)partial, P, C, sg.chunk, neg, H, W); }); });
-    }
-    else if (h == nullptr)
-        hipLaunchKernelGGL((reduce_stage1<T, 1, false>), grid, dim3(MG_NTHR), 0, st,
-                           (const T*)x, (const T*)dh, (const T*)h, (const T*)g1, mean, rstd, (T*)dgb,
-                           (float*)partial, P, C, sg.tpr, sg.rpb, sg.chunk, act, slope, up, H, W);
-    else
-        hipLaunchKernelGGL((reduce_stage1<T, 1, true>), grid, dim3(MG_NTHR), 0, st,
-                           (const T*)x, (const T*)dh, (const T*)h, (const T*)g1, mean, rstd, (T*)dgb,
-                           (float*)partial, P, C, sg.tpr, sg.rpb, sg.chunk, act, slope, up, H, W);
+    } else
+        mg_by_bool(h != nullptr, [&](auto hh) {
+            hipLaunchKernelGGL((bwd_stage1_quad<T, hh.value>), grid, dim3(MG_NTHR), 0, st, (const T*)x, (const T*)dh, (const T*)h, (const T*)g1,
+                               mean, rstd, (T*)dgb, (float*)partial, P, C, sg.tpr, sg.rpb, sg.chunk, act, slope, up, H, W); });
     MG_CHECK_LAUNCH("reduce_stage1");
     dim3 grid2((2 * C + 31) / 32, G);
     hipLaunchKernelGGL(reduce_stage2, grid2, dim3(256), 0, st, (const float*)partial, sums, sg.nchunks, 2 * C);
@@ -697,8 +638,8 @@ int run_reduce(const void* x, const void* dh, const void* h, const void* g1, con
 }  // namespace
 
 #define MG_CHECK_NORM_GEOM(name) \
-    MG_CHECK_ARG(dtype == MG_F32 || dtype == MG_BF16, name ": bad dtype %d", dtype); \
-    MG_CHECK_ARG(G > 0 && P > 0 && C > 0 && (C % 4) == 0 && C <= 4096, name ": bad geometry G=%d P=%ld C=%d (C must be a multiple of 4, <= 4096)", G, (long)P, C)
+    MG_CHECK_ARG(dtype == MG_F32 || dtype == MG_BF16, "%s: bad dtype %d", name, dtype); \
+    MG_CHECK_ARG(G > 0 && P > 0 && C > 0 && (C % 4) == 0 && C <= 4096, "%s: bad geometry G=%d P=%ld C=%d (C must be a multiple of 4, <= 4096)", name, G, (long)P, C)
 
 extern "C" int64_t mg_stats_workspace(int32_t G, int64_t P, int32_t C)
 {
@@ -739,9 +680,8 @@ extern "C" int mg_norm_act_fwd(const void* x, void* y, int32_t dtype, int32_t G,
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t nq = (int64_t)G * P * (C / 4);
     mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
-        if (act != MG_ACT_TANH && vec_geom_ok<T>(C)) {
-            const int rows = MG_NTHR / (C / VT<T>::VEC);
-            hipLaunchKernelGGL((norm_act_fwd_vec<T, 4>), dim3(pix_grid(P, rows, 4, G), G), dim3(MG_NTHR), 0, st,
+        if (takes_vec<T>(C, act)) {
+            hipLaunchKernelGGL((norm_act_fwd_vec<T, 4>), dim3(pix_grid(P, vec_rows<T>(C), 4, G), G), dim3(MG_NTHR), 0, st,
                                (const T*)x, (T*)y, P, C, mean, rstd, mg_neg_slope(act, slope), act == MG_ACT_RELU, (const T*)resid);
         } else
             hipLaunchKernelGGL(norm_act_fwd_kernel<T>, dim3(mg_ew_grid(nq, 8192)), dim3(MG_NTHR), 0, st,
@@ -751,17 +691,26 @@ extern "C" int mg_norm_act_fwd(const void* x, void* y, int32_t dtype, int32_t G,
     return MG_OK;
 }
 
+// what mg_norm_bwd_reduce and mg_norm_bwd_reduce_up check and launch; up: P = N * H * W pixels read x through a nearest 2x upsample
+static int norm_bwd_reduce(const char* name, const void* dh, const void* h, const void* x, const void* g1,
+                           int32_t dtype, int32_t G, int64_t P, int32_t C, const float* mean, const float* rstd, int32_t act, float slope,
+                           void* dgb, float* sums, void* partial, void* stream, int up, int32_t N, int32_t H, int32_t W)
+{
+    MG_CHECK_NORM_GEOM(name);
+    MG_CHECK_ARG(dh && (h || act == MG_ACT_NONE) && x && mean && rstd && sums && partial, "%s: null pointer", name);
+    MG_CHECK_ARG(dgb == nullptr || G == 1, "%s: dgb output requires G == 1", name);
+    if (up) MG_CHECK_ARG(N > 0 && H > 0 && W > 0 && (H % 2) == 0 && (W % 2) == 0 && P < (1L << 31), "%s: H, W must be even", name);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        return run_reduce<T>(x, dh, h, g1, mean, rstd, dgb, G, P, C, sums, partial, act, slope, st, up, H, W); });
+}
+
 extern "C" int mg_norm_bwd_reduce(const void* dh, const void* h, const void* x, const void* g1,
                                   int32_t dtype, int32_t G, int64_t P, int32_t C,
                                   const float* mean, const float* rstd, int32_t act, float slope,
                                   void* dgb, float* sums, void* partial, void* stream)
 {
-    MG_CHECK_NORM_GEOM("mg_norm_bwd_reduce");
-    MG_CHECK_ARG(dh && (h || act == MG_ACT_NONE) && x && mean && rstd && sums && partial, "mg_norm_bwd_reduce: null pointer");
-    MG_CHECK_ARG(dgb == nullptr || G == 1, "mg_norm_bwd_reduce: dgb output requires G == 1");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
-        return run_reduce<T>(x, dh, h, g1, mean, rstd, dgb, G, P, C, sums, partial, act, slope, st); });
+    return norm_bwd_reduce("mg_norm_bwd_reduce", dh, h, x, g1, dtype, G, P, C, mean, rstd, act, slope, dgb, sums, partial, stream, 0, 0, 0, 0);
 }
 
 extern "C" int mg_norm_bwd_reduce_up(const void* dh, const void* h, const void* x, const void* g1,
@@ -769,25 +718,18 @@ extern "C" int mg_norm_bwd_reduce_up(const void* dh, const void* h, const void* 
                                      const float* mean, const float* rstd, int32_t act, float slope,
                                      void* dgb, float* sums, void* partial, void* stream)
 {
-    const int32_t G = 1; const int64_t P = (int64_t)N * H * W;
-    MG_CHECK_NORM_GEOM("mg_norm_bwd_reduce_up");
-    MG_CHECK_ARG(dh && (h || act == MG_ACT_NONE) && x && mean && rstd && sums && partial, "mg_norm_bwd_reduce_up: null pointer");
-    MG_CHECK_ARG(N > 0 && H > 0 && W > 0 && (H % 2) == 0 && (W % 2) == 0 && P < (1L << 31), "mg_norm_bwd_reduce_up: H, W must be even");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
-        return run_reduce<T>(x, dh, h, g1, mean, rstd, dgb, G, P, C, sums, partial, act, slope, st, 1, H, W); });
+    return norm_bwd_reduce("mg_norm_bwd_reduce_up", dh, h, x, g1, dtype, 1, (int64_t)N * H * W, C, mean, rstd, act, slope, dgb, sums, partial, stream, 1, N, H, W);
 }
 
 template <typename T>
 static int launch_apply2(const mg_norm_apply2_desc& d, hipStream_t st)
 {
-    constexpr int VEC = VT<T>::VEC;
-    const int rows = MG_NTHR / (d.C / VEC);
+    const int rows = vec_rows<T>(d.C);
     const bool two = d.dh[1] != nullptr;
     const int64_t pout = d.up ? d.P / 4 : d.P;
     const float n0 = mg_neg_slope(d.act[0], d.slope[0]), n1 = mg_neg_slope(d.act[1], d.slope[1]);
     const dim3 grid(pix_grid(pout, rows, 1, 1)), blk(MG_NTHR);
-    by_bool(d.up != 0, [&](auto up) { by_bool(two, [&](auto nb2) {
+    mg_by_bool(d.up != 0, [&](auto up) { mg_by_bool(two, [&](auto nb2) {
         hipLaunchKernelGGL((norm_bwd_apply2_vec<T, nb2.value ? 2 : 1, up.value>), grid, blk, 0, st, d, n0, n1); }); });
     return 0;
 }
@@ -826,9 +768,8 @@ extern "C" int mg_norm_bwd_apply(const void* dh, const void* h, const void* x, c
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t nq = (int64_t)G * P * (C / 4);
     mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
-        if (act != MG_ACT_TANH && vec_geom_ok<T>(C)) {
-            const int rows = MG_NTHR / (C / VT<T>::VEC);
-            hipLaunchKernelGGL((norm_bwd_apply_vec<T, 2>), dim3(pix_grid(P, rows, 2, G), G), dim3(MG_NTHR), 0, st,
+        if (takes_vec<T>(C, act)) {
+            hipLaunchKernelGGL((norm_bwd_apply_vec<T, 2>), dim3(pix_grid(P, vec_rows<T>(C), 2, G), G), dim3(MG_NTHR), 0, st,
                                (const T*)dh, (const T*)h, (const T*)x, (const T*)g1, (T*)dx,
                                P, C, mean, rstd, s1, s2, sgs, sscale, mg_neg_slope(act, slope));
         } else

@@ -737,6 +737,11 @@ def _wgrad_launch(x, dy, taps, stride, want_bias, out=None, beside=False):
     return (dw, dbias) if want_bias else dw
 
 
+def _stats_workspace(groups: int, p: int, c: int, device) -> torch.Tensor:
+    """The stage-1 partial sums of a [G, P, C] column reduction (mg_stats_workspace bytes, never an empty tensor)."""
+    return torch.empty(max(int(C.backend().mg_stats_workspace(groups, p, c)), 4), dtype=torch.uint8, device=device)
+
+
 def channel_sums(x: torch.Tensor, groups: int = 1, shift: bool = False) -> torch.Tensor:
     """x viewed as [G, P, C] -> fp64 [G, 2, C] (sum, sum of squares); deterministic two-stage reduce (fp32 partial sums per chunk,
     fp64 across chunks: mg_norm.hip).  `shift`: accumulate x - x[g, 0, c] and un-shift in fp64 -- for STATISTICS (the variance must
@@ -744,7 +749,7 @@ def channel_sums(x: torch.Tensor, groups: int = 1, shift: bool = False) -> torch
     c = x.shape[-1]
     p = x.numel() // (groups * c)
     be = C.backend()
-    ws = torch.empty(max(int(be.mg_stats_workspace(groups, p, c)), 4), dtype=torch.uint8, device=x.device)
+    ws = _stats_workspace(groups, p, c, x.device)
     sums = torch.empty((groups, 2, c), dtype=torch.float64, device=x.device)
     be.mg_channel_stats(_p(x), _dt(x), groups, p, c, int(shift), _p(sums), _p(ws), _stream(x))
     return sums
@@ -945,7 +950,7 @@ def stats_finalize(x: torch.Tensor, groups: int, count: float, eps: float, momen
     c = x.shape[-1]
     p = x.numel() // (groups * c)
     be = C.backend()
-    ws = torch.empty(max(int(be.mg_stats_workspace(groups, p, c)), 4), dtype=torch.uint8, device=x.device)
+    ws = _stats_workspace(groups, p, c, x.device)
     sums = torch.empty((groups, 2, c), dtype=torch.float64, device=x.device)
     mean = torch.empty((groups, c), dtype=torch.float32, device=x.device)
     rstd = torch.empty((groups, c), dtype=torch.float32, device=x.device)
@@ -1125,7 +1130,7 @@ def _spade_branch_reduce(dh, h, g1, x, mean, rstd, act, slope, sums, up=False):
     be = C.backend()
     alloc = torch.zeros if rows != 2 * c else torch.empty      # padded gamma/beta rows must read 0
     dgb = alloc((n, hh, ww, rows), dtype=x.dtype, device=x.device)
-    ws = torch.empty(max(int(be.mg_stats_workspace(1, p, c)), 4), dtype=torch.uint8, device=x.device)
+    ws = _stats_workspace(1, p, c, x.device)
     if _grad_premasked(dh, h, act):
         act = ACT_NONE                               # conv_0 / conv_1's data-gradient epilogue already applied the LeakyReLU mask
     hp = _p(h) if act != ACT_NONE else None          # the activation's output is only read for its sign
@@ -1317,7 +1322,7 @@ class _InstanceNormActFn(torch.autograd.Function):
         p = h * w
         be = C.backend()
         sums = torch.empty((n, 2, c), dtype=torch.float32, device=x.device)
-        ws = torch.empty(max(int(be.mg_stats_workspace(n, p, c)), 4), dtype=torch.uint8, device=x.device)
+        ws = _stats_workspace(n, p, c, x.device)
         be.mg_norm_bwd_reduce(_p(dy), _p(y), _p(x), None, _dt(x), n, p, c, _p(mean), _p(rstd), act, slope,
                               None, _p(sums), _p(ws), _stream(x))
         dx = torch.empty_like(x)

@@ -15,6 +15,23 @@ Three entry points whose per-element terms are exact, so the model needs no kern
 The inputs must discriminate: for every case the model is also evaluated with the pairwise join and as one plain left-to-right sum over
 all elements, and at least one of the two has to differ in bits from the documented order (checked before the kernel's result is looked at).
 
+The per-channel (column) sums of mg_norm.hip follow the header's second order:
+
+    thread row tr adds pixels p0 + tr, p0 + tr + rows, ... of its chunk sequentially from +0  ->  rows are added in ascending order.
+
+The fp32 `partial` workspace [G][chunk][2][C] is held to that model bit for bit; stat_geom() below mirrors StatGeom / vec_geom_ok of
+michigan_amd/csrc/mg_norm.hip (chunking; thread rows of the channel-resident "vec" and of the quad kernels).  Exact per-element terms again:
+  mg_channel_stats       shift = 0: x and x * x; x holds <= 12 significant bits (fp32) or is bf16, so the square is exact, fma or not
+  mg_norm_bwd_reduce     mean = 0, rstd = 1, act none, no h / g1 / dgb: dh and dh * x; at both values of OPT_NORM_BWD_VEC on a vec-capable
+                         geometry.  The two kernels give the same bits where their thread rows are as many (fp32: VEC = 4 is the quad);
+                         bf16 C = 32 has 64 vec rows against 32 quad rows, two different orders, and each is held to its own model
+  mg_norm_bwd_reduce_up  the same with x the half-resolution source, read at (y >> 1, x >> 1)
+Operands: seeded normals x 2^k, k uniform in -8 .. 8 per element (without the exponent spread as few as 1 of 32 columns tells the orders
+apart).  Discrimination is checked first: per half of `partial`, at least a quarter of the entries must differ in bits from the chunk summed
+in plain pixel order (where rows > 1) and from a pairwise tree over the chunk's pixels.  COLUMN_CASES have 3, 5, 3, 3 chunks and the _up
+case 4, each with a ragged last row trip.  The fp64 finish: `sums` equals the float64 sum of `partial` over the chunks (plus the un-shift,
+0 here), which is exact in any order for operands this narrow.
+
 The fp64 halving trees are NOT pinned here: an order change in fp64 over at most 1024 fp32 partials almost never survives the cast to
 float.  They are held by mg_grad_drain's double output (tests/test_gpu_census.py) and by comparing every output before against after a
 change of these kernels.  The pairwise join of mg_feat_moments.hip is held by the style-loss tests.
@@ -177,3 +194,155 @@ def test_sn_normalize_adds_in_the_documented_order(backend, n):
     _cabi.backend().mg_sn_normalize(ops._p(td), n, SN_EPS, ops._p(dst), None, None, ops._stream(td))
     got = dst.cpu().numpy()
     assert same(got, doc), f"sn_normalize n={n}: {int((bits(got) != bits(doc)).sum())} of {n} quotients differ from the documented order's"
+
+
+# =====================================================================================================================
+# column sums (mg_norm.hip): the row join of mg_reduce.h
+# =====================================================================================================================
+def stat_geom(dt, G, P, C):
+    """StatGeom stat_geom(G, P, C) and vec_geom_ok<T>(C) of michigan_amd/csrc/mg_norm.hip: (chunk, nchunks, quad rows, vec rows or None)."""
+    tpr = min(C // 4, 256)
+    rpb = 256 // tpr
+    want = max(min(-(-1536 // G), -(-P // (rpb * 16)), 512), 1)
+    chunk = -(-P // want)
+    vec = 8 if dt == "bf16" else 4
+    cv = C // vec
+    vec_rows = 256 // cv if C % vec == 0 and cv <= 256 and 256 % cv == 0 else None
+    return chunk, -(-P // chunk), rpb, vec_rows
+
+
+def column_operand(seed, shape, dt):
+    rng = np.random.default_rng(seed)
+    v = rng.standard_normal(shape) * np.exp2(rng.integers(-8, 9, shape))
+    if dt == "bf16":
+        return torch.from_numpy(v.astype(F32)).to(torch.bfloat16)
+    m, e = np.frexp(v)
+    return torch.from_numpy(np.ldexp(np.round(m * 4096.0) / 4096.0, e).astype(F32))          # 12 significant bits
+
+
+def pairwise_rows(t):
+    """[n, ...] -> the pairwise tree over axis 0 (an odd level is padded with +0)."""
+    while t.shape[0] > 1:
+        if t.shape[0] & 1:
+            t = np.concatenate([t, np.zeros_like(t[:1])])
+        t = t[0::2] + t[1::2]
+    return t[0]
+
+
+def column_model(terms, chunk, rows):
+    """terms [G, P, C] fp32 (exact per-element terms) -> (documented, plain pixel order, pairwise), each [G, nchunks, C]."""
+    G, P, C = terms.shape
+    out = []
+    for g in range(G):
+        per = []
+        for p0 in range(0, P, chunk):
+            t = terms[g, p0:p0 + chunk]
+            trips = -(-t.shape[0] // rows)
+            pad = np.zeros((trips * rows, C), F32)
+            pad[:t.shape[0]] = t                                             # a row's missing last trip adds +0: no bit changes
+            own = seq_sum(pad.reshape(trips, rows, C).transpose(1, 2, 0))     # [rows, C]: row tr adds p0 + tr, p0 + tr + rows, ...
+            per.append((seq_sum(own.T), seq_sum(t.T), pairwise_rows(t)))
+        out.append([np.stack(z) for z in zip(*per)])
+    return [np.stack(z) for z in zip(*out)]
+
+
+def check_discriminates(tag, doc, plain, pair, rows):
+    for name, alt in (("plain pixel order", plain), ("pairwise tree", pair)):
+        if name == "plain pixel order" and rows == 1:
+            continue                                                        # one thread row adds in pixel order
+        differ = int((bits(doc) != bits(alt)).sum())
+        if 4 * differ < doc.size:
+            raise RuntimeError(f"{tag}: only {differ} of {doc.size} entries tell the documented order from the {name}")
+
+
+def column_case(tag, dt, x, dh, chunk, nchunks, rows_list, run, x_terms=None):
+    """run(i) -> (partial [G, nchunks, 2, C] fp32, sums [G, 2, C]) for rows_list[i]; dh None: the statistics terms x, x * x."""
+    xf = (x if x_terms is None else x_terms).float().numpy()
+    halves = (xf, xf * xf) if dh is None else (dh.float().numpy(), dh.float().numpy() * xf)
+    models = {}
+    for rows in set(rows_list):
+        models[rows] = [column_model(h, chunk, rows) for h in halves]
+        for name, (doc, plain, pair) in zip(("sum", "sum of products"), models[rows]):
+            assert doc.shape[1] == nchunks
+            check_discriminates(f"{tag} rows={rows} {name}", doc, plain, pair, rows)
+    got = []
+    for i, rows in enumerate(rows_list):
+        partial, sums = run(i)
+        partial, sums = partial.cpu().numpy(), sums.cpu().numpy()
+        for k, name in enumerate(("sum", "sum of products")):
+            doc = models[rows][k][0]
+            differ = int((bits(partial[:, :, k]) != bits(doc)).sum())
+            print(f"[order] {tag} rows={rows} {name}: {differ} of {doc.size} partial sums differ from the documented order")
+            assert differ == 0, f"{tag} rows={rows} {name}: {differ} of {doc.size} partial sums differ from the documented order"
+        want = np.add.accumulate(partial.astype(np.float64), axis=1)[:, -1]          # [G, 2, C]: exact for these operands
+        assert np.array_equal(sums, want.astype(sums.dtype)), f"{tag} rows={rows}: sums is not the float64 sum of partial"
+        got.append(partial)
+    for i in range(1, len(got)):
+        if rows_list[i] == rows_list[0]:
+            assert same(got[i], got[0]), f"{tag}: the two kernels differ in bits at equal thread rows"
+
+
+# (dtype, C, G, P): vec cv 8 rows 32 | vec cv 4 rows 64 | quad tpr 6 rpb 42 | quad tpr 256, two channel trips, rows 1
+COLUMN_CASES = [("f32", 32, 2, 1500), ("bf16", 32, 1, 2100), ("f32", 24, 1, 1400), ("f32", 1032, 1, 40)]
+COLUMN_ROWS = {("f32", 32): (32, 32), ("bf16", 32): (32, 64), ("f32", 24): (42, None), ("f32", 1032): (1, None)}      # (quad, vec)
+
+
+def _geom(dt, G, P, C, be):
+    chunk, nchunks, rpb, vec_rows = stat_geom(dt, G, P, C)
+    assert (rpb, vec_rows) == COLUMN_ROWS[(dt, C)] and nchunks >= 3, (chunk, nchunks, rpb, vec_rows)
+    assert all(chunk % r for r in (rpb, vec_rows) if r and r > 1), "no ragged last row trip"
+    assert int(be.mg_stats_workspace(G, P, C)) == G * nchunks * 2 * C * 4, "stat_geom() here no longer mirrors mg_norm.hip"
+    return chunk, nchunks, rpb, vec_rows
+
+
+@pytest.mark.parametrize("dt,C,G,P", COLUMN_CASES)
+def test_channel_stats_add_in_the_documented_order(backend, dt, C, G, P):
+    from michigan_amd import ops
+    chunk, nchunks, rpb, vec_rows = _geom(dt, G, P, C, backend)
+    x = column_operand(400 + C + P, (G, P, C), dt)
+    xd = x.cuda()
+
+    def run(i):
+        partial = torch.full((G, nchunks, 2, C), float("nan"), dtype=torch.float32, device="cuda")
+        sums = torch.empty((G, 2, C), dtype=torch.float64, device="cuda")
+        backend.mg_channel_stats(ops._p(xd), ops._dt(xd), G, P, C, 0, ops._p(sums), ops._p(partial), ops._stream(xd))
+        return partial, sums
+    column_case(f"stats {dt} C={C} G={G} P={P}", dt, x, None, chunk, nchunks, [vec_rows or rpb], run)
+
+
+def _bwd_reduce_case(backend, tag, dt, C, G, P, up=None):
+    from michigan_amd import _cabi, ops
+    chunk, nchunks, rpb, vec_rows = _geom(dt, G, P, C, backend)
+    dh = column_operand(500 + C + P, (G, P, C), dt)
+    if up is None:
+        x = x_full = column_operand(600 + C + P, (G, P, C), dt)
+    else:
+        n, hh, ww = up
+        x = column_operand(600 + C + P, (n, hh // 2, ww // 2, C), dt)
+        yy, xx = np.arange(hh) >> 1, np.arange(ww) >> 1
+        x_full = x[:, yy][:, :, xx].reshape(1, P, C)                         # what pixel (y, x) reads: the source at (y >> 1, x >> 1)
+    dhd, xd = dh.cuda(), x.cuda()
+    mean, rstd = torch.zeros((G, C), dtype=torch.float32, device="cuda"), torch.ones((G, C), dtype=torch.float32, device="cuda")
+    variants = [(0, rpb)] + ([(1, vec_rows)] if vec_rows else [])             # (OPT_NORM_BWD_VEC, thread rows of the kernel it selects)
+
+    def run(i):
+        partial = torch.full((G, nchunks, 2, C), float("nan"), dtype=torch.float32, device="cuda")
+        sums = torch.empty((G, 2, C), dtype=torch.float32, device="cuda")
+        with _cabi.options({_cabi.OPT_NORM_BWD_VEC: variants[i][0]}):
+            if up is None:
+                backend.mg_norm_bwd_reduce(ops._p(dhd), None, ops._p(xd), None, ops._dt(xd), G, P, C, ops._p(mean), ops._p(rstd), 0, 0.0,
+                                           None, ops._p(sums), ops._p(partial), ops._stream(xd))
+            else:
+                backend.mg_norm_bwd_reduce_up(ops._p(dhd), None, ops._p(xd), None, ops._dt(xd), up[0], up[1], up[2], C, ops._p(mean), ops._p(rstd), 0, 0.0,
+                                              None, ops._p(sums), ops._p(partial), ops._stream(xd))
+        return partial, sums
+    column_case(tag, dt, x, dh, chunk, nchunks, [r for _, r in variants], run, x_terms=x_full)
+
+
+@pytest.mark.parametrize("dt,C,G,P", COLUMN_CASES)
+def test_norm_bwd_reduce_adds_in_the_documented_order(backend, dt, C, G, P):
+    _bwd_reduce_case(backend, f"bwd reduce {dt} C={C} G={G} P={P}", dt, C, G, P)
+
+
+def test_norm_bwd_reduce_up_adds_in_the_documented_order(backend):
+    _bwd_reduce_case(backend, "bwd reduce up f32 C=32 1x40x40", "f32", 32, 1, 1600, up=(1, 40, 40))
