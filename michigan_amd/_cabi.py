@@ -19,6 +19,7 @@ MG_MAX_TAPS = 64
 MG_ABI_VERSION = 9
 MG_COMM_ID_BYTES = 128
 MG_EXT_FEATURE_LOSSES = 1                  # include/michigan_hip/feature_losses.h: what mg_ext_version() returns
+MG_PREP_DENSE_ORIENT = 1                   # include/michigan_hip/preprocess/dense_orient.h: what mg_prep_version() returns
 
 # enum mg_option (include/michigan_hip.h): the tuning switches of mg_set_option / mg_get_option; OPT_PROBE_* exist in -DMG_PROBES=1 builds only
 OPT_CONV_BIGTILES, OPT_CONV_HALO, OPT_WGRAD3X3, OPT_CONV_HALO_BIG, OPT_CONV_SPLITK, OPT_CONV_THIN, OPT_CONV_WIDE, OPT_CONV_DOT = 1, 2, 3, 4, 5, 6, 7, 8
@@ -197,8 +198,15 @@ _EXT_PROTOS = {
     "mg_feat_moment_loss_bwd": ([ctypes.POINTER(FeatMomentDesc), _vp, _vp, _vp, _vp], _i32),
 }
 EXTENSION_SYMBOLS = tuple(_EXT_PROTOS)
+# The preprocessing group (include/michigan_hip/preprocess/*.h): a third table with the same obligations (tests/test_dense_orient.py).  It is
+# a table of its own because tests/test_cabi_extensions.py ties every device-writing name of _EXT_PROTOS to a guarded case in ONE test file.
+_PREP_PROTOS = {
+    "mg_prep_version": ([], _i32),
+    "mg_orient_smooth": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp], _i32),
+}
+PREPROCESS_SYMBOLS = tuple(_PREP_PROTOS)
 _NO_STATUS = {"mg_wgrad_det_workspace", "mg_norm_apply2_supported", "mg_grad_slot_blocks", "mg_pack_job_blocks", "mg_sn_layer_blocks", "mg_stats_workspace", "mg_sizeof_desc", "mg_abi_version", "mg_last_error", "mg_noise_field_len", "mg_bicubic_ksize",
-              "mg_ext_version", "mg_feat_moment_workspace"}
+              "mg_ext_version", "mg_feat_moment_workspace", "mg_prep_version"}
 
 LIB_PATH = os.environ.get("MG_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmichigan_hip.so")   # MG_LIB: a measurement variant (tools/build_variant.py)
 
@@ -223,7 +231,7 @@ class HipBackend:
         # torch must already have loaded its libamdhip64 so that we bind to the same runtime.
         import torch  # noqa: F401
         self._lib = ctypes.CDLL(path)
-        for table in (_PROTOS, _EXT_PROTOS):
+        for table in (_PROTOS, _EXT_PROTOS, _PREP_PROTOS):
             for fn, (argtypes, restype) in table.items():
                 f = getattr(self._lib, fn)          # AttributeError if a symbol is missing
                 f.argtypes, f.restype = argtypes, restype
@@ -231,6 +239,8 @@ class HipBackend:
             raise RuntimeError("libmichigan_hip.so ABI version mismatch")
         if self._lib.mg_ext_version() != MG_EXT_FEATURE_LOSSES:
             raise RuntimeError("libmichigan_hip.so extension-group version mismatch (michigan_hip/feature_losses.h)")
+        if self._lib.mg_prep_version() != MG_PREP_DENSE_ORIENT:
+            raise RuntimeError("libmichigan_hip.so preprocessing-group version mismatch (michigan_hip/preprocess/dense_orient.h)")
         if (self._lib.mg_sizeof_desc(0) != ctypes.sizeof(ConvDesc) or self._lib.mg_sizeof_desc(1) != ctypes.sizeof(WgradDesc)
                 or self._lib.mg_sizeof_desc(2) != ctypes.sizeof(GradSlot) or self._lib.mg_sizeof_desc(3) != ctypes.sizeof(PackJob)
                 or self._lib.mg_sizeof_desc(4) != ctypes.sizeof(SnLayer) or self._lib.mg_sizeof_desc(5) != ctypes.sizeof(NormApply2Desc)
@@ -238,7 +248,7 @@ class HipBackend:
             raise RuntimeError("ctypes mirror of the descriptor structs is out of sync with include/michigan_hip.h")
 
     def __getattr__(self, fn):
-        if fn not in _PROTOS and fn not in _EXT_PROTOS:
+        if fn not in _PROTOS and fn not in _EXT_PROTOS and fn not in _PREP_PROTOS:
             raise AttributeError(fn)
         raw = getattr(self._lib, fn)
         if fn in _NO_STATUS:

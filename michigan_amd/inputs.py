@@ -12,6 +12,7 @@ same arithmetic runs here as HIP kernels of libmichigan_hip.so on u8 maps that w
     generate_hole_u8   generate_hole
     generate_noise     generate_noise (multi-octave, cv2.resize INTER_LINEAR)
     resize_bicubic_u8  get_transform's Resize(BICUBIC) for images (Pillow's 8-bit resampler)
+    dense_orientation  cal_orientation.py: the uint8 orientation map itself, from an image and its hair mask
 
 `DeviceInputPipeline` strings them together into the `data` dict of pix2pix_dataset.py:178-188.  The random
 DRAWS stay on the host and follow the reference (random.randint / random.random / random.uniform of a
@@ -165,6 +166,44 @@ def generate_noise(n: int, size: int, device, generator: Optional[torch.Generato
     """base_dataset.py:387-396 for a batch: np.random.normal(0.5, 0.25) fields drawn on the device."""
     fields = torch.randn((n, noise_field_len(size)), dtype=torch.float64, device=device, generator=generator) * 0.25 + 0.5
     return noise_from_fields(fields, size)
+
+
+_DOG_BANKS = {}
+
+
+def dense_orientation(image: torch.Tensor, mask: torch.Tensor, sigma: float = 4.0, return_angle: bool = False):
+    """cal_orientation.py for a batch on the device: the uint8 dense orientation map [N,H,W] of `image` under the hair `mask` --
+    what orient_to_rgb_u8, DeviceInputPipeline and the orientation loss read (with return_angle also the fp32 angle in [0, pi]).
+
+    image: fp32 in [-1, 1], [N,3,H,W] or [N,H,W,3], or uint8 RGB in either layout (converted as ToTensor + Normalize(0.5) do, in fp32,
+    so that the gray image keeps the reference's roundings).  bf16 is refused: an 8-bit mantissa moves the arg-max over the filters.
+    mask: integer or float [N,H,W]; a mask whose maximum is above 1 is thresholded at > 130 (cal_orientation.py:91-92).
+    Two launches: mg_gabor_argmax_fwd under ops.dog_bank (calOrientation, lines 60-80), then mg_orient_smooth (lines 101-109)."""
+    from . import ops
+    if image.dim() != 4 or (image.shape[-1] != 3 and image.shape[1] != 3):
+        raise ValueError(f"dense_orientation: image must be [N,3,H,W] or [N,H,W,3], got {tuple(image.shape)}")
+    if image.dtype == torch.uint8:
+        image = ((image.to(torch.float32) / 255) - 0.5) / 0.5
+    elif image.dtype != torch.float32:
+        raise ValueError(f"dense_orientation: image must be fp32 or uint8, got {image.dtype} (bf16 moves the arg-max)")
+    if image.shape[-1] != 3:
+        image = image.permute(0, 2, 3, 1)
+    n, h, w, _ = image.shape
+    if mask.dim() == 4 and mask.shape[1] == 1:
+        mask = mask[:, 0]
+    if tuple(mask.shape) != (n, h, w):
+        raise ValueError(f"dense_orientation: mask {tuple(mask.shape)} does not match the image's {(n, h, w)}")
+    if h <= ops.ORIENT_RADIUS or w <= ops.ORIENT_RADIUS:
+        raise ValueError(f"dense_orientation: H and W must be at least {ops.ORIENT_RADIUS + 1}, got {h} x {w}")
+    ops.gaussian_taps(sigma)                                              # refuses sigma before anything is launched
+    mask = mask.to(image.device)
+    hair = ((mask > 130) if float(mask.max()) > 1 else (mask != 0)).to(torch.uint8)
+    dev = str(image.device)
+    if dev not in _DOG_BANKS:
+        _DOG_BANKS[dev] = ops.dog_bank(image.device)
+    with torch.no_grad():
+        conf, idx = ops.gabor_argmax(image.contiguous(), _DOG_BANKS[dev])
+    return ops.orient_smooth(conf, idx, hair, sigma=sigma, want_angle=return_angle)
 
 
 class DeviceInputPipeline:

@@ -2220,6 +2220,72 @@ def gabor_argmax(img_nhwc: torch.Tensor, bank: torch.Tensor):
     return _GaborMaxFn.apply(img_nhwc, bank)
 
 
+def dog_bank(device=None) -> torch.Tensor:
+    """The 32 oriented 17x17 difference-of-Gaussians kernels of dense orientation extraction, fp32 [32, 17, 17]
+    (cal_orientation.py:18-44: sigma_h 1, sigma_l 2, sigma_y 2, theta_k = pi k / 32, normalised by 1/sigma_h - 1/sigma_l;
+    x runs along rows).  With this bank mg_gabor_argmax_fwd is orient.calOrientation (cal_orientation.py:60-80)."""
+    import math
+    r = torch.arange(-8, 9, dtype=torch.float32)
+    x = r.view(-1, 1).expand(17, 17)
+    y = r.view(1, -1).expand(17, 17)
+    theta = torch.tensor([math.pi * k / 32 for k in range(32)], dtype=torch.float32).view(-1, 1, 1)    # rounded once, as the reference's
+    xt = x * torch.cos(theta) + y * torch.sin(theta)
+    yt = -x * torch.sin(theta) + y * torch.cos(theta)
+    gb = (torch.exp(-0.5 * (xt ** 2 / 1.0 ** 2 + yt ** 2 / 2.0 ** 2)) / 1.0
+          - torch.exp(-0.5 * (xt ** 2 / 2.0 ** 2 + yt ** 2 / 2.0 ** 2)) / 2.0) / (1.0 / 1.0 - 1.0 / 2.0)
+    return gb.contiguous().to(device) if device is not None else gb.contiguous()
+
+
+def orient_trig_table() -> torch.Tensor:
+    """fp32 [32, 2]: (cos, sin) of the angle filter index k stands for in the flow field, k * pi / 31 * 2, evaluated in fp32 in the
+    reference's order of operations (cal_orientation.py:101-104; the 31 is the reference's own (sic): the bank steps by pi / 32)."""
+    import math
+    a = torch.arange(32, dtype=torch.float32) * math.pi / 31 * 2
+    return torch.stack([torch.cos(a), torch.sin(a)], dim=1).contiguous()
+
+
+ORIENT_RADIUS = 16                      # MG_ORIENT_RADIUS (include/michigan_hip/preprocess/dense_orient.h)
+ORIENT_MAX_SIGMA = 4.0                  # the 33-tap window is cv2's for sigma = 4; a larger sigma would be truncated below 4 sigma
+
+
+def gaussian_taps(sigma: float) -> torch.Tensor:
+    """fp32 [33]: exp(-x^2 / (2 sigma^2)) for x = -16 .. 16, normalised in float64 -- the window of cv2.GaussianBlur(src_f32, (0, 0), 4)
+    (ksize = round(sigma * 4 * 2 + 1) | 1 = 33 for a float source).  0 < sigma <= 4; below 4 the window reaches further than cv2's."""
+    if not 0.0 < float(sigma) <= ORIENT_MAX_SIGMA:
+        raise ValueError(f"gaussian_taps: sigma must be in (0, {ORIENT_MAX_SIGMA}], got {sigma}")
+    x = torch.arange(-ORIENT_RADIUS, ORIENT_RADIUS + 1, dtype=torch.float64)
+    t = torch.exp(-x * x / (2.0 * float(sigma) ** 2))
+    return (t / t.sum()).float().contiguous()
+
+
+_ORIENT_TABLES = {}
+
+
+def _orient_tables(device, sigma: float):
+    key = (str(device), float(sigma))
+    if key not in _ORIENT_TABLES:
+        _ORIENT_TABLES[key] = (orient_trig_table().to(device), gaussian_taps(sigma).to(device))
+    return _ORIENT_TABLES[key]
+
+
+def orient_smooth(conf: torch.Tensor, idx: torch.Tensor, mask: torch.Tensor, sigma: float = 4.0, want_angle: bool = False):
+    """cal_orientation.py:101-109 in one launch (mg_orient_smooth): conf fp32 / idx u8 [N,H,W] of gabor_argmax under dog_bank, mask u8
+    [N,H,W] (non-zero = hair) -> the uint8 orientation map [N,H,W] (and the fp32 angle in [0, pi] when want_angle)."""
+    if conf.dim() != 3 or conf.dtype != torch.float32 or idx.dtype != torch.uint8 or mask.dtype != torch.uint8:
+        raise ValueError("orient_smooth: conf must be fp32 [N,H,W], idx and mask uint8")
+    if idx.shape != conf.shape or mask.shape != conf.shape:
+        raise ValueError(f"orient_smooth: shapes differ: conf {tuple(conf.shape)}, idx {tuple(idx.shape)}, mask {tuple(mask.shape)}")
+    n, h, w = conf.shape
+    if n < 1 or h <= ORIENT_RADIUS or w <= ORIENT_RADIUS:
+        raise ValueError(f"orient_smooth: H and W must be at least {ORIENT_RADIUS + 1} (one reflection reaches every tap), got {h} x {w}")
+    trig, taps = _orient_tables(conf.device, sigma)
+    conf, idx, mask = conf.contiguous(), idx.contiguous(), mask.contiguous()
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=conf.device)
+    angle = torch.empty((n, h, w), dtype=torch.float32, device=conf.device) if want_angle else None
+    C.backend().mg_orient_smooth(_p(conf), _p(idx), _p(mask), _p(trig), _p(taps), _p(out), _p(angle), n, h, w, _stream(conf))
+    return (out, angle) if want_angle else out
+
+
 def self_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[n, i] = sum_j softmax_j(q[n, i] . k[n, j]) v[n, j] over the L positions of each sample (generator.py:467-485; no 1/sqrt(d)
     scale), inference only.  q, k: [N, L, 64], v: [N, L, 256] in the compute dtype; each may be a column slice of a wider row-major
