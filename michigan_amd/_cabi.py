@@ -20,6 +20,7 @@ MG_ABI_VERSION = 9
 MG_COMM_ID_BYTES = 128
 MG_EXT_FEATURE_LOSSES = 1                  # include/michigan_hip/feature_losses.h: what mg_ext_version() returns
 MG_PREP_DENSE_ORIENT = 1                   # include/michigan_hip/preprocess/dense_orient.h: what mg_prep_version() returns
+MG_EDIT_STROKE = 1                         # include/michigan_hip/editing/stroke_orient.h: what mg_edit_version() returns
 
 # enum mg_option (include/michigan_hip.h): the tuning switches of mg_set_option / mg_get_option; OPT_PROBE_* exist in -DMG_PROBES=1 builds only
 OPT_CONV_BIGTILES, OPT_CONV_HALO, OPT_WGRAD3X3, OPT_CONV_HALO_BIG, OPT_CONV_SPLITK, OPT_CONV_THIN, OPT_CONV_WIDE, OPT_CONV_DOT = 1, 2, 3, 4, 5, 6, 7, 8
@@ -205,8 +206,17 @@ _PREP_PROTOS = {
     "mg_orient_smooth": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp], _i32),
 }
 PREPROCESS_SYMBOLS = tuple(_PREP_PROTOS)
+# The editing group (include/michigan_hip/editing/*.h): the stroke route of the interactive demo, a fourth table for the same reason
+# (tests/test_stroke.py holds it to the obligations; its guarded cases live in tests/test_gpu_stroke.py).
+_EDIT_PROTOS = {
+    "mg_edit_version": ([], _i32),
+    "mg_stroke_orient": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp], _i32),
+    "mg_stroke_compose": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
+    "mg_inpaint_finish": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp], _i32),
+}
+EDITING_SYMBOLS = tuple(_EDIT_PROTOS)
 _NO_STATUS = {"mg_wgrad_det_workspace", "mg_norm_apply2_supported", "mg_grad_slot_blocks", "mg_pack_job_blocks", "mg_sn_layer_blocks", "mg_stats_workspace", "mg_sizeof_desc", "mg_abi_version", "mg_last_error", "mg_noise_field_len", "mg_bicubic_ksize",
-              "mg_ext_version", "mg_feat_moment_workspace", "mg_prep_version"}
+              "mg_ext_version", "mg_feat_moment_workspace", "mg_prep_version", "mg_edit_version"}
 
 LIB_PATH = os.environ.get("MG_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmichigan_hip.so")   # MG_LIB: a measurement variant (tools/build_variant.py)
 
@@ -231,7 +241,7 @@ class HipBackend:
         # torch must already have loaded its libamdhip64 so that we bind to the same runtime.
         import torch  # noqa: F401
         self._lib = ctypes.CDLL(path)
-        for table in (_PROTOS, _EXT_PROTOS, _PREP_PROTOS):
+        for table in (_PROTOS, _EXT_PROTOS, _PREP_PROTOS, _EDIT_PROTOS):
             for fn, (argtypes, restype) in table.items():
                 f = getattr(self._lib, fn)          # AttributeError if a symbol is missing
                 f.argtypes, f.restype = argtypes, restype
@@ -241,6 +251,8 @@ class HipBackend:
             raise RuntimeError("libmichigan_hip.so extension-group version mismatch (michigan_hip/feature_losses.h)")
         if self._lib.mg_prep_version() != MG_PREP_DENSE_ORIENT:
             raise RuntimeError("libmichigan_hip.so preprocessing-group version mismatch (michigan_hip/preprocess/dense_orient.h)")
+        if self._lib.mg_edit_version() != MG_EDIT_STROKE:
+            raise RuntimeError("libmichigan_hip.so editing-group version mismatch (michigan_hip/editing/stroke_orient.h)")
         if (self._lib.mg_sizeof_desc(0) != ctypes.sizeof(ConvDesc) or self._lib.mg_sizeof_desc(1) != ctypes.sizeof(WgradDesc)
                 or self._lib.mg_sizeof_desc(2) != ctypes.sizeof(GradSlot) or self._lib.mg_sizeof_desc(3) != ctypes.sizeof(PackJob)
                 or self._lib.mg_sizeof_desc(4) != ctypes.sizeof(SnLayer) or self._lib.mg_sizeof_desc(5) != ctypes.sizeof(NormApply2Desc)
@@ -248,7 +260,7 @@ class HipBackend:
             raise RuntimeError("ctypes mirror of the descriptor structs is out of sync with include/michigan_hip.h")
 
     def __getattr__(self, fn):
-        if fn not in _PROTOS and fn not in _EXT_PROTOS and fn not in _PREP_PROTOS:
+        if fn not in _PROTOS and fn not in _EXT_PROTOS and fn not in _PREP_PROTOS and fn not in _EDIT_PROTOS:
             raise AttributeError(fn)
         raw = getattr(self._lib, fn)
         if fn in _NO_STATUS:

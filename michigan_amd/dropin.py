@@ -205,6 +205,7 @@ def install(compute_dtype: Optional[str] = "fp32", losses: bool = True, data_par
 
     G = _net_class(hip.SPADEBGenerator, ref_base, dtype, "models.networks.generator")
     IG = _net_class(hip.InpaintGenerator, ref_base, dtype, "models.networks.generator")
+    SIG = _net_class(hip.SInpaintGenerator, ref_base, dtype, "models.networks.generator")
     D = _net_class(hip.MultiscaleDiscriminator, ref_base, dtype, "models.networks.discriminator")
     ND = _net_class(hip.NLayerDiscriminator, ref_base, dtype, "models.networks.discriminator")
 
@@ -221,9 +222,9 @@ def install(compute_dtype: Optional[str] = "fp32", losses: bool = True, data_par
     if dtype is not None:
         vgg_ns["compute_dtype"] = dtype
     V = type("VGG19", (hip.VGG19,), vgg_ns)
-    patched = {"SPADEBGenerator": G, "InpaintGenerator": IG, "MultiscaleDiscriminator": D, "NLayerDiscriminator": ND, "VGG19": V}
+    patched = {"SPADEBGenerator": G, "InpaintGenerator": IG, "SInpaintGenerator": SIG, "MultiscaleDiscriminator": D, "NLayerDiscriminator": ND, "VGG19": V}
 
-    for name in ("SPADEBGenerator", "InpaintGenerator"):
+    for name in ("SPADEBGenerator", "InpaintGenerator", "SInpaintGenerator"):     # (--use_stroke: util.load_sinpainting_network loads its file as is)
         _set("models.networks.generator", name, patched[name])
         _set("models.networks", name, patched[name])                  # `from models.networks.generator import *` copies
     for name in ("MultiscaleDiscriminator", "NLayerDiscriminator"):

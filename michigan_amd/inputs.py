@@ -13,6 +13,8 @@ same arithmetic runs here as HIP kernels of libmichigan_hip.so on u8 maps that w
     generate_noise     generate_noise (multi-octave, cv2.resize INTER_LINEAR)
     resize_bicubic_u8  get_transform's Resize(BICUBIC) for images (Pillow's 8-bit resampler)
     dense_orientation  cal_orientation.py: the uint8 orientation map itself, from an image and its hair mask
+    stroke_to_orient   ui_util/cal_orient_stroke.py: the RGB-coded orientation picture of a drawn stroke mask
+    stroke_inputs      demo_inference_dataLoad's orient_stroke / mask_stroke / hole tensors (base_dataset.py:214-238)
 
 `DeviceInputPipeline` strings them together into the `data` dict of pix2pix_dataset.py:178-188.  The random
 DRAWS stay on the host and follow the reference (random.randint / random.random / random.uniform of a
@@ -204,6 +206,48 @@ def dense_orientation(image: torch.Tensor, mask: torch.Tensor, sigma: float = 4.
     with torch.no_grad():
         conf, idx = ops.gabor_argmax(image.contiguous(), _DOG_BANKS[dev])
     return ops.orient_smooth(conf, idx, hair, sigma=sigma, want_angle=return_angle)
+
+
+def _stroke_mask_u8(mask_stroke: torch.Tensor) -> torch.Tensor:
+    """[N,H,W] / [H,W] / [N,1,H,W] of any integer or float dtype -> uint8 [N,H,W], np.uint8's truncation for float maps"""
+    m = mask_stroke
+    if m.dim() == 2:
+        m = m.unsqueeze(0)
+    if m.dim() == 4 and m.shape[1] == 1:
+        m = m[:, 0]
+    if m.dim() != 3:
+        raise ValueError(f"a stroke mask must be [H,W], [N,H,W] or [N,1,H,W], got {tuple(mask_stroke.shape)}")
+    if m.dtype == torch.bfloat16 or m.dtype == torch.float16:
+        raise ValueError(f"a stroke mask must be an integer, fp32 or fp64 map, got {m.dtype}")
+    return m.to(torch.uint8).contiguous()
+
+
+def stroke_to_orient(mask_stroke: torch.Tensor) -> torch.Tensor:
+    """np.uint8(orient().stroke_to_orient(m)) (ui_util/cal_orient_stroke.py:133-149; demo.py:326) for a batch on the device:
+    mask_stroke [N,H,W] (or [H,W], [N,1,H,W]), non-zero = stroke (the reference's masks are in {0, 1}) -> the RGB-coded orientation picture u8 [N,H,W,3], black outside the stroke.
+    One launch (mg_stroke_orient); a tile of the canvas without a stroke pixel costs nothing but its zeros."""
+    from . import ops
+    return ops.stroke_orient(_stroke_mask_u8(mask_stroke))     # non-zero = stroke; nothing is read back: a pen lift does not wait for the device
+
+
+def stroke_inputs(mask_stroke: torch.Tensor, label_tag: torch.Tensor, mask_hole: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The stroke entries of demo_inference_dataLoad's batch (base_dataset.py:214-238) at the size of label_tag [N,1,H,W] (the class
+    index map as fp32): orient_stroke [N,3,H,W] = ToTensor(stroke picture) * label_tag, mask_stroke [N,1,H,W] = ToTensor(mask) * 255 *
+    label_tag and, when mask_hole is given (the caller dilates the stroke: demo.py:323-324), hole likewise."""
+    m = _stroke_mask_u8(mask_stroke)
+    n, h, w = m.shape
+    label = label_tag.to(device=m.device, dtype=torch.float32)
+    if tuple(label.shape) != (n, 1, h, w):
+        raise ValueError(f"stroke_inputs: label_tag must be {(n, 1, h, w)}, got {tuple(label_tag.shape)}")
+    zero = torch.zeros((n, 3), dtype=torch.int32)                           # no crop, no flip: the demo works at the crop size
+    out = {"orient_stroke": crop_u8(stroke_to_orient(m), zero, (h, w), mode=2, mul=label),
+           "mask_stroke": crop_u8(m, zero, (h, w), mode=1, mul=label)}
+    if mask_hole is not None:
+        hm = _stroke_mask_u8(mask_hole.to(m.device))
+        if hm.shape != m.shape:
+            raise ValueError(f"stroke_inputs: mask_hole {tuple(mask_hole.shape)} does not match the stroke mask's {tuple(m.shape)}")
+        out["hole"] = crop_u8(hm, zero, (h, w), mode=1, mul=label)
+    return out
 
 
 class DeviceInputPipeline:

@@ -14,7 +14,9 @@ objective is GAN + ORIENT (+ CONFIDENCE) + hairAvgLab + background (pix2pix_mode
 pass (mg_hair_lab_*).  The style / content terms (pix2pix_model.py:309-319, on by default in the reference, switched off by the
 README command and by `default_options()`) are fused feature-moment passes over the VGG taps (mg_feat_moment_loss_*), computed at
 `curr_step == 1` whether or not the reference is the target, on the tower pass the VGG loss already pays for.  balance_Lab and the
-blender are outside this tier's scope.
+blender are outside this tier's scope.  Mode 'demo_inference' (pix2pix_model.py:94-120) is the interactive demo's call:
+with `use_stroke` a second frozen net (netSIG) fills the hole around the user's strokes (`inpainting_stroke_orient`), and the call returns the
+generated image and the in-painted orientation picture.
 
 Differences that do not change results (SURVEY.md section 8a "parity-preserving minimum"):
   * the discriminator's parameters do not require grad during the generator step (their
@@ -80,6 +82,8 @@ def default_options(**over) -> argparse.Namespace:
         no_style_loss=True, no_content_loss=True, lambda_style=1.0, lambda_content=1.0,
         # the unpaired training stage (train_options.py:38-41): netD2 + hairAvgLab at curr_step == 2
         unpairTrain=False, lambda_hairavglab=1.0, same_netD_model=False,
+        # the stroke route of the interactive demo (base_options.py:118-121): a second frozen net, used by mode 'demo_inference'
+        use_stroke=False, inpaint_mode="ref", netSIG="sinpaint",
     )
     d.update(over)
     return argparse.Namespace(**d)
@@ -117,21 +121,30 @@ class Pix2PixModel(nn.Module):
             self.netIG = networks.define_IG(opt).eval()          # frozen (pix2pix_model.py:196-198)
             for p in self.netIG.parameters():
                 p.requires_grad_(False)
+        self.netSIG = None
+        if getattr(opt, "use_stroke", False):
+            self.netSIG = networks.define_SIG(opt).eval()        # frozen (pix2pix_model.py:199-201)
+            for p in self.netSIG.parameters():
+                p.requires_grad_(False)
 
     # -- data ---------------------------------------------------------------------
-    def preprocess_input(self, data: Dict[str, torch.Tensor]):
+    def preprocess_input(self, data: Dict[str, torch.Tensor], demo: bool = False):
         """Accepts either the reference's loader dict (label_tag/label_ref index maps, pix2pix_model.py:209-254)
-        or already one-hot maps (michigan_amd.synth.synth_batch)."""
+        or already one-hot maps (michigan_amd.synth.synth_batch).  The stroke entries of the demo's loader (orient_stroke,
+        mask_stroke, orient_rgb_mask; base_dataset.py:214-238, 253-255) are carried along when present.  demo: mode
+        'demo_inference', whose `orient` is replaced by an in-painted map whichever net is built (see demo_inference)."""
         dev = next(self.netG.parameters()).device
         out = {}
-        for k in ("input_tag", "input_ref", "image_tag", "image_ref", "orient", "noise", "hole", "orient_rgb"):
+        for k in ("input_tag", "input_ref", "image_tag", "image_ref", "orient", "noise", "hole", "orient_rgb",
+                  "orient_stroke", "mask_stroke", "orient_rgb_mask"):
             if k in data:
                 out[k] = data[k].to(dev, non_blocking=True)
         for src, dst in (("label_tag", "input_tag"), ("label_ref", "input_ref")):
             if dst not in out:
                 nc = self.opt.label_nc + (1 if self.opt.contain_dontcare_label else 0)
                 out[dst] = inputs.onehot_labels(data[src].to(dev), nc)        # zeros().scatter_(1, label.long(), 1.0)
-        self._check_orientation(out)
+        if not demo:
+            self._check_orientation(out)
         return out
 
     def _check_orientation(self, d):
@@ -173,6 +186,49 @@ class Pix2PixModel(nn.Module):
         out = out * hole + orient_rgb * (1 - hole)
         o2 = (out[:, :-1] - 0.5) * 2
         return out, torch.stack([o2[:, 1], o2[:, 0]], dim=1) * mask
+
+    def inpainting_stroke_orient(self, hole, orient_rgb, noise, mask, stroke, stroke_mask, mask_orient_rgb):
+        """pix2pix_model.py:431-464: where the hair mask reaches beyond the known orientation (mask - mask_orient_rgb is not zero
+        everywhere) that part is in-painted first by the reference-orientation net (inpainting_orient, as the reference does); then
+        the hole around the strokes is filled by the stroke net, which sees the strokes themselves in the hole.  The net's input is
+        assembled by one launch in its own layout at 256 x 256 (ops.stroke_compose) and its output blended, resampled and turned
+        into the 2-channel orientation by another (ops.inpaint_finish).  Returns (RGB map in [0,1], 2-channel orientation x mask)."""
+        from . import ops
+        if self.netSIG is None:
+            raise RuntimeError("inpainting_stroke_orient: the stroke in-painting net is not built (opt.use_stroke)")
+        first = mask - mask_orient_rgb
+        if torch.max(first) != 0:
+            if getattr(self, "netIG", None) is None:
+                raise RuntimeError("inpainting_stroke_orient: the hair mask reaches beyond the known orientation, which the reference "
+                                   "in-paints first with netIG (opt.inpaint_orient); it is not built")
+            orient_rgb, _ = self.inpainting_orient(first, orient_rgb, noise, mask)
+        size = (256, 256) if self.opt.crop_size != 256 else None
+        inp = ops.stroke_compose(orient_rgb, noise, hole, stroke, stroke_mask, size=size, dtype=self.netSIG.compute_dtype)
+        return ops.inpaint_finish(self.netSIG.forward_nhwc8(inp), hole, orient_rgb, mask)
+
+    def demo_inference(self, d):
+        """mode 'demo_inference' (pix2pix_model.py:94-120): (fake_image, orient_out).  orient_out is the in-painted RGB orientation
+        map as the demo shows it, uint8 [N,H,W,3] = trunc(out_rgb * 255) on the device (the reference's numpy value is
+        orient_out[0].cpu().numpy()); None without use_ig."""
+        orient_out = None
+        if self.opt.use_ig:
+            stroke = "stroke" in getattr(self.opt, "inpaint_mode", "ref")
+            needs = ("hole", "orient_rgb", "noise") + (("orient_stroke", "mask_stroke", "orient_rgb_mask") if stroke else ())
+            missing = [k for k in needs if k not in d]
+            if missing:
+                raise ValueError("demo_inference (inpaint_mode %r): the batch lacks %s" % (self.opt.inpaint_mode, missing))
+            hair = d["input_tag"][:, 1:2]
+            if stroke:
+                rgb, orient = self.inpainting_stroke_orient(d["hole"], d["orient_rgb"], d["noise"], hair, d["orient_stroke"], d["mask_stroke"],
+                                                            d["orient_rgb_mask"])
+            else:
+                if self.netIG is None:
+                    raise RuntimeError("demo_inference (inpaint_mode 'ref'): the in-painting net is not built (opt.inpaint_orient)")
+                rgb, orient = self.inpainting_orient(d["hole"], d["orient_rgb"], d["noise"], hair)
+            orient_out = (rgb.permute(0, 2, 3, 1) * 255).to(torch.uint8)
+            d = dict(d)
+            d["orient"] = orient
+        return self.generate_fake(d), orient_out
 
     def _maybe_inpaint(self, d):
         if self.netIG is None:
@@ -396,6 +452,9 @@ class Pix2PixModel(nn.Module):
                 "D_real": self.criterionGAN(pred_real, True, for_discriminator=True, label=label)}
 
     def forward(self, data, mode):
+        if mode == "demo_inference":
+            with torch.no_grad():
+                return self.demo_inference(self.preprocess_input(data, demo=True))
         d = self.preprocess_input(data)
         if mode == "generator":
             return self.compute_generator_loss(d)
@@ -472,6 +531,8 @@ class Pix2PixTrainer:
                 parallel.broadcast_parameters(self.pix2pix_model.netD2)
             if self.pix2pix_model.netIG is not None:
                 parallel.broadcast_parameters(self.pix2pix_model.netIG)
+            if self.pix2pix_model.netSIG is not None:
+                parallel.broadcast_parameters(self.pix2pix_model.netSIG)
         self.optimizer_D2 = None
         if getattr(opt, "unpairTrain", False):               # pix2pix_trainer.py:30-33
             self.optimizer_G, self.optimizer_D, self.optimizer_D2 = self.pix2pix_model.create_optimizers(opt, group)

@@ -17,7 +17,7 @@ from .base_network import BaseNetwork
 from .discriminator import MultiscaleDiscriminator, NLayerDiscriminator
 from .encoder import BackgroundEncode2, ConvBlock, ImageEncoder3, PartialConv2d
 from .generator import SPADEBGenerator
-from .inpaint import InpaintGenerator
+from .inpaint import InpaintGenerator, SInpaintGenerator
 from .loss import GANFeatLoss, GANLoss, HairAvgLabLoss, L1OLoss, LabColorLoss, RGBBackgroundL1Loss, StyleContentLoss, VGGLoss
 from .normalization import SPADE, SegPyramid, get_nonspade_norm_layer
 from .sync_batchnorm import DataParallelWithCallback, SynchronizedBatchNorm2d
@@ -27,7 +27,7 @@ __all__ = [
     "SPADE", "SegPyramid", "VGG19", "ImageEncoder3", "BackgroundEncode2", "PartialConv2d", "ConvBlock",
     "GANLoss", "GANFeatLoss", "VGGLoss", "L1OLoss", "LabColorLoss", "RGBBackgroundL1Loss", "HairAvgLabLoss", "StyleContentLoss", "SynchronizedBatchNorm2d", "DataParallelWithCallback",
     "get_nonspade_norm_layer", "find_network_using_name", "modify_commandline_options", "create_network",
-    "define_G", "define_D", "define_IG", "InpaintGenerator",
+    "define_G", "define_D", "define_IG", "define_SIG", "InpaintGenerator", "SInpaintGenerator",
 ]
 
 
@@ -82,3 +82,8 @@ def define_D(opt):
 def define_IG(opt):
     """The frozen orientation in-painting generator (`--use_ig`, models/networks/__init__.py:70-72)."""
     return create_network(find_network_using_name(getattr(opt, "netIG", "inpaint"), "generator"), opt)
+
+
+def define_SIG(opt):
+    """The frozen stroke in-painting generator (`--use_stroke`, models/networks/__init__.py:74-76)."""
+    return create_network(find_network_using_name(getattr(opt, "netSIG", "sinpaint"), "generator"), opt)

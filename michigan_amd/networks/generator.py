@@ -137,4 +137,4 @@ class SPADEBGenerator(BaseNetwork):
 
 # `--netIG inpaint` resolves through find_network_using_name(opt.netIG, "generator") exactly like the reference
 # (models/networks/__init__.py:70-72), so the class has to be visible in this module's namespace.
-from .inpaint import InpaintGenerator  # noqa: E402,F401
+from .inpaint import InpaintGenerator, SInpaintGenerator  # noqa: E402,F401

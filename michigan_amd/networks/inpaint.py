@@ -1,7 +1,7 @@
 """The frozen orientation in-painting network (`--use_ig`): inference only.
 
-Reference: models/networks/generator.py:450-575 (`ResnetBlock`, `SelfAttention`, `InpaintGenerator`, skips=False) and
-its caller models/pix2pix_model.py:407-429.  Parameters, buffers and nn.Sequential indices are the reference's, so its
+Reference: models/networks/generator.py:450-575 (`ResnetBlock`, `SelfAttention`, `InpaintGenerator`, skips=False), :577-665
+(`SInpaintGenerator`, the same body on five input channels) and their callers models/pix2pix_model.py:407-464.  Parameters, buffers and nn.Sequential indices are the reference's, so its
 `InpaintingModel_gen.pth` checkpoints load unchanged.  The network runs at 256x256 without gradients:
 7x7 / 4x4-stride-2 / dilated 3x3 / transposed 4x4 convolutions on the MFMA tap-list kernels (the transposed ones as
 per-parity-class gathers), InstanceNorm(+ReLU/LeakyReLU) on the fused norm kernels, reflection padding on the gather
@@ -117,13 +117,17 @@ class SelfAttention(nn.Module):
 
 
 class InpaintGenerator(BaseNetwork):
+    """The frozen in-painting body; `in_channels` is what the first convolution reads: 4 (RGB-coded orientation + hole) here, 5 in
+    SInpaintGenerator (+ the stroke mask)."""
+    in_channels = 4
+
     def __init__(self, opt, blocks=12, skips=False):
         super().__init__()
         if skips:
-            raise NotImplementedError("InpaintGenerator: the skip-connection variant is not used by the reference's options")
+            raise NotImplementedError("%s: the skip-connection variant is not used by the reference's options" % type(self).__name__)
         self.skips = skips
         self.encoder = nn.Sequential(
-            nn.ReflectionPad2d(3), _sn(InferConv2d(4, 64, 7, padding=0)), nn.InstanceNorm2d(64), nn.LeakyReLU(0.2, True),
+            nn.ReflectionPad2d(3), _sn(InferConv2d(self.in_channels, 64, 7, padding=0)), nn.InstanceNorm2d(64), nn.LeakyReLU(0.2, True),
             _sn(InferConv2d(64, 128, 4, stride=2, padding=1)), nn.InstanceNorm2d(128), nn.LeakyReLU(0.2, True),
             _sn(InferConv2d(128, 256, 4, stride=2, padding=1)), nn.InstanceNorm2d(256), nn.LeakyReLU(0.2, True))
         self.middle = nn.Sequential(*[ResnetBlock(256) for _ in range(blocks)], SelfAttention(256))
@@ -133,9 +137,16 @@ class InpaintGenerator(BaseNetwork):
             nn.ReflectionPad2d(3), InferConv2d(64, 3, 7, padding=0))
 
     @torch.no_grad()
-    def forward(self, x):                                   # NCHW [N, 4, H, W] -> NCHW [N, 3, H, W] in [0, 1]
+    def forward(self, x):                                   # NCHW [N, in_channels, H, W] -> NCHW [N, 3, H, W] in [0, 1]
+        return self.forward_nhwc8(ops.pad_channels(ops.to_nhwc(x, self.compute_dtype), 8))
+
+    @torch.no_grad()
+    def forward_nhwc8(self, y):
+        """The same on an input already in the kernels' layout: [N, H, W, 8] in the compute dtype, channels in_channels .. 7 zero
+        (what ops.stroke_compose writes)."""
+        if y.dim() != 4 or y.shape[-1] != 8 or y.dtype != self.compute_dtype:
+            raise ValueError("%s.forward_nhwc8: expected [N,H,W,8] %s, got %s %s" % (type(self).__name__, self.compute_dtype, tuple(y.shape), y.dtype))
         e, d = self.encoder, self.decoder
-        y = ops.pad_channels(ops.to_nhwc(x, self.compute_dtype), 8)
         y = ops.instance_norm_act(e[1].infer(ops.reflect_pad(y, 3)), act=ops.ACT_LRELU, slope=0.2)
         y = ops.instance_norm_act(e[4].infer(y), act=ops.ACT_LRELU, slope=0.2)
         y = ops.instance_norm_act(e[7].infer(y), act=ops.ACT_LRELU, slope=0.2)
@@ -144,3 +155,9 @@ class InpaintGenerator(BaseNetwork):
         y = ops.instance_norm_act(d[3].infer(y), act=ops.ACT_RELU)
         y = d[7].infer(ops.reflect_pad(y, 3), act=ops.ACT_TANH)
         return (ops.to_nchw(y).float()[:, :3] + 1) / 2
+
+
+class SInpaintGenerator(InpaintGenerator):
+    """The stroke in-painting net (`--use_stroke`, `--netSIG sinpaint`; generator.py:577-665): the same body on five input channels
+    (RGB-coded orientation, hole, stroke mask), so the reference's SInpaintingModel_gen.pth loads unchanged."""
+    in_channels = 5

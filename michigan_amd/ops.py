@@ -2286,6 +2286,120 @@ def orient_smooth(conf: torch.Tensor, idx: torch.Tensor, mask: torch.Tensor, sig
     return (out, angle) if want_angle else out
 
 
+def stroke_rgb_table() -> torch.Tensor:
+    """u8 [32, 3]: the colour the stroke picture gives filter index k (cal_orient_stroke.py:112-115, 123-149): a = fp32(k) * pi / 32,
+    (R, G, B) = uint8((v + 1) / 2 * 255) for v = (cos 2a, sin 2a, 0), every step in fp32 in the reference's order."""
+    import math
+    a = torch.arange(32, dtype=torch.float32) * math.pi / 32
+    v = torch.stack([torch.cos(2 * a), torch.sin(2 * a), torch.zeros(32)], dim=1)
+    return ((v + 1) / 2.0 * 255.0).to(torch.uint8).contiguous()        # np.uint8 of a value in [0, 255]: truncation
+
+
+_STROKE_TABLES = {}
+
+
+def _stroke_tables(device):
+    key = str(device)
+    if key not in _STROKE_TABLES:
+        _STROKE_TABLES[key] = (dog_bank().to(device), stroke_rgb_table().to(device))
+    return _STROKE_TABLES[key]
+
+
+def stroke_orient(stroke: torch.Tensor, want_idx: bool = False, want_conf: bool = False, bank: Optional[torch.Tensor] = None):
+    """orient().stroke_to_orient (cal_orient_stroke.py:85-121, 133-149) in one launch (mg_stroke_orient): stroke u8 [N,H,W], non-zero =
+    stroke -> the RGB-coded orientation picture u8 [N,H,W,3], black outside the stroke (and the filter index u8 / the confidence
+    fp32 [N,H,W] when asked for).  Tiles without a stroke pixel are not filtered.  `bank`: another fp32 [32,17,17] bank than dog_bank()."""
+    if stroke.dim() != 3 or stroke.dtype != torch.uint8:
+        raise ValueError(f"stroke_orient: stroke must be uint8 [N,H,W], got {stroke.dtype} {tuple(stroke.shape)}")
+    n, h, w = stroke.shape
+    if n < 1 or h < 1 or w < 1 or n * h * w >= 1 << 31:
+        raise ValueError(f"stroke_orient: bad geometry {tuple(stroke.shape)} (N H W must be in [1, 2^31))")
+    dog, table = _stroke_tables(stroke.device)
+    if bank is None:
+        bank = dog
+    elif bank.dtype != torch.float32 or tuple(bank.shape) != (32, 17, 17) or bank.device != stroke.device:
+        raise ValueError(f"stroke_orient: bank must be fp32 [32,17,17] on {stroke.device} (bf16 moves the arg-max), got {bank.dtype} {tuple(bank.shape)} on {bank.device}")
+    bank = bank.contiguous()
+    stroke = stroke.contiguous()
+    rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=stroke.device)
+    idx = torch.empty((n, h, w), dtype=torch.uint8, device=stroke.device) if want_idx else None
+    conf = torch.empty((n, h, w), dtype=torch.float32, device=stroke.device) if want_conf else None
+    C.backend().mg_stroke_orient(_p(stroke), _p(bank), _p(table), _p(rgb), _p(idx), _p(conf), n, h, w, _stream(stroke))
+    extra = tuple(t for t in (idx, conf) if t is not None)
+    return (rgb,) + extra if extra else rgb
+
+
+def interp_nearest_table(src: int, dst: int, device=None) -> Optional[torch.Tensor]:
+    """int32 [dst]: the source index F.interpolate(mode='nearest') reads for each of `dst` outputs of a `src`-long axis -- taken from
+    F.interpolate itself on an arange, so it is that function's rule by construction.  None = identity (src == dst)."""
+    import torch.nn.functional as F
+    src, dst = int(src), int(dst)
+    if src < 1 or dst < 1 or src >= 1 << 24:
+        raise ValueError(f"interp_nearest_table: bad sizes {src} -> {dst} (an index above 2^24 is not exact in fp32)")
+    if src == dst:
+        return None
+    t = F.interpolate(torch.arange(src, dtype=torch.float32).view(1, 1, 1, src), size=(1, dst), mode="nearest").view(dst).to(torch.int32)
+    return t.to(device) if device is not None else t
+
+
+_INTERP_TABLES = {}
+
+
+def _interp_table(src: int, dst: int, device):
+    key = (int(src), int(dst), str(device))
+    if key not in _INTERP_TABLES:
+        _INTERP_TABLES[key] = interp_nearest_table(src, dst, device)
+    return _INTERP_TABLES[key]
+
+
+def _planes(name, t, c, n, h, w):
+    if t.dtype != torch.float32 or tuple(t.shape) != (n, c, h, w):
+        raise ValueError(f"{name} must be fp32 {(n, c, h, w)}, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def stroke_compose(orient_rgb: torch.Tensor, noise: torch.Tensor, hole: torch.Tensor, stroke: Optional[torch.Tensor] = None,
+                   stroke_mask: Optional[torch.Tensor] = None, size=None, dtype=torch.float32) -> torch.Tensor:
+    """The in-painting net's input in its own layout, in one launch (mg_stroke_compose; pix2pix_model.py:443-447, and 408-411 when
+    stroke / stroke_mask are None): NCHW fp32 maps at H x W -> NHWC8 `dtype` at `size` (nearest, F.interpolate's rule), channels
+    0-2 = orient_rgb (1 - hole) + noise (hole - stroke_mask) + stroke stroke_mask, 3 = hole, 4 = stroke_mask, 5-7 = 0."""
+    if orient_rgb.dim() != 4 or orient_rgb.shape[1] != 3:
+        raise ValueError(f"stroke_compose: orient_rgb must be [N,3,H,W], got {tuple(orient_rgb.shape)}")
+    if (stroke is None) != (stroke_mask is None):
+        raise ValueError("stroke_compose: stroke and stroke_mask are given together or not at all")
+    n, _, h, w = orient_rgb.shape
+    ho, wo = (h, w) if size is None else ((size, size) if isinstance(size, int) else tuple(size))
+    orient_rgb, noise, hole = _planes("stroke_compose: orient_rgb", orient_rgb, 3, n, h, w), _planes("stroke_compose: noise", noise, 3, n, h, w), _planes("stroke_compose: hole", hole, 1, n, h, w)
+    if stroke is not None:
+        stroke, stroke_mask = _planes("stroke_compose: stroke", stroke, 3, n, h, w), _planes("stroke_compose: stroke_mask", stroke_mask, 1, n, h, w)
+    code = _dtype_code(dtype)
+    ytab, xtab = _interp_table(h, ho, orient_rgb.device), _interp_table(w, wo, orient_rgb.device)
+    inp = torch.empty((n, ho, wo, 8), dtype=dtype, device=orient_rgb.device)
+    C.backend().mg_stroke_compose(_p(orient_rgb), _p(noise), _p(hole), _p(stroke), _p(stroke_mask), _p(ytab), _p(xtab), code, n, h, w, ho, wo,
+                                  _p(inp), _stream(orient_rgb))
+    return inp
+
+
+def inpaint_finish(net_out: torch.Tensor, hole: torch.Tensor, orient_rgb: torch.Tensor, mask: torch.Tensor):
+    """What becomes of the in-painting net's output, in one launch (mg_inpaint_finish; pix2pix_model.py:450-463): net_out fp32
+    [N,3,Ho,Wo] -> (out_rgb [N,3,H,W] = up(net_out) hole + orient_rgb (1 - hole), orient2 [N,2,H,W] = ((out_rgb[1] - 0.5) 2 mask,
+    (out_rgb[0] - 0.5) 2 mask)), `up` being F.interpolate(mode='nearest') to the size of orient_rgb."""
+    if orient_rgb.dim() != 4 or orient_rgb.shape[1] != 3:
+        raise ValueError(f"inpaint_finish: orient_rgb must be [N,3,H,W], got {tuple(orient_rgb.shape)}")
+    n, _, h, w = orient_rgb.shape
+    if net_out.dim() != 4 or net_out.dtype != torch.float32 or net_out.shape[:2] != (n, 3):
+        raise ValueError(f"inpaint_finish: net_out must be fp32 [{n},3,Ho,Wo], got {net_out.dtype} {tuple(net_out.shape)}")
+    ho, wo = net_out.shape[2:]
+    orient_rgb, hole, mask = _planes("inpaint_finish: orient_rgb", orient_rgb, 3, n, h, w), _planes("inpaint_finish: hole", hole, 1, n, h, w), _planes("inpaint_finish: mask", mask, 1, n, h, w)
+    net_out = net_out.contiguous()
+    ytab, xtab = _interp_table(ho, h, orient_rgb.device), _interp_table(wo, w, orient_rgb.device)
+    out_rgb = torch.empty((n, 3, h, w), dtype=torch.float32, device=orient_rgb.device)
+    orient2 = torch.empty((n, 2, h, w), dtype=torch.float32, device=orient_rgb.device)
+    C.backend().mg_inpaint_finish(_p(net_out), _p(ytab), _p(xtab), _p(hole), _p(orient_rgb), _p(mask), n, h, w, ho, wo, _p(out_rgb), _p(orient2),
+                                  _stream(orient_rgb))
+    return out_rgb, orient2
+
+
 def self_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[n, i] = sum_j softmax_j(q[n, i] . k[n, j]) v[n, j] over the L positions of each sample (generator.py:467-485; no 1/sqrt(d)
     scale), inference only.  q, k: [N, L, 64], v: [N, L, 256] in the compute dtype; each may be a column slice of a wider row-major
