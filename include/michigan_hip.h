@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MG_ABI_VERSION 9
+#define MG_ABI_VERSION 10
 
 enum { MG_F32 = 0, MG_BF16 = 1 };
 enum { MG_ACT_NONE = 0, MG_ACT_RELU = 1, MG_ACT_LRELU = 2, MG_ACT_TANH = 3 };
@@ -591,8 +591,9 @@ enum mg_option {
 int         mg_set_option(int32_t key, int32_t value);
 int         mg_get_option(int32_t key, int32_t* value);
 
-/* sizeof(mg_conv_desc) (which=0) / sizeof(mg_wgrad_desc) (which=1): lets a
- * foreign-language binding check its struct mirror without a GPU. */
+/* sizeof of a descriptor struct -- which = 0 mg_conv_desc, 1 mg_wgrad_desc, 2 mg_grad_slot, 3 mg_pack_job, 4 mg_sn_layer,
+ * 5 mg_norm_apply2_desc, 6 mg_pyramid_desc, 7 mg_feat_moment_desc; -1 otherwise: lets a foreign-language binding check its
+ * struct mirror without a GPU. */
 int         mg_sizeof_desc(int32_t which);
 int         mg_abi_version(void);
 const char* mg_last_error(void);
@@ -600,4 +601,12 @@ const char* mg_last_error(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* The entry points of the feature losses, the dense-orientation preprocessing and the stroke editing route are declared in
+ * headers of their own, next to the tile and radius constants their kernels are compiled from.  They belong to this ABI like
+ * everything above: including michigan_hip.h declares all of it. */
+#include "michigan_hip/feature_losses.h"
+#include "michigan_hip/preprocess/dense_orient.h"
+#include "michigan_hip/editing/stroke_orient.h"
+
 #endif /* MICHIGAN_HIP_H */

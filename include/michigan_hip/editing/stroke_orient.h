@@ -1,12 +1,7 @@
-/* michigan_hip/editing/stroke_orient.h -- editing group of libmichigan_hip: the stroke route of the interactive demo (mg_stroke.hip).
+/* michigan_hip/editing/stroke_orient.h -- part of the C ABI of libmichigan_hip (michigan_hip.h includes it): the stroke route of the interactive demo (mg_stroke.hip).
  * Reference: ui_util/cal_orient_stroke.py:85-121, 133-149 (orient.stroke_to_orient: the drawn stroke mask under the 32
  * difference-of-Gaussians filters, first arg-max, the RGB-coded orientation picture) and models/pix2pix_model.py:431-464
  * (inpainting_stroke_orient: the input of the frozen stroke in-painting net and what is made of its output).
- *
- * AN EDITING GROUP is an extension group (see michigan_hip/feature_losses.h) in a directory of its own: every mg_*( declared under
- * michigan_hip/editing/ is mirrored in michigan_amd/_cabi.py (_EDIT_PROTOS / EDITING_SYMBOLS), exported by the library, and -- where it
- * writes device memory -- has a guarded case in tests/test_gpu_stroke.py (tests/test_stroke.py holds the group to this).  It has a
- * version of its own (mg_edit_version); MG_ABI_VERSION, mg_ext_version, mg_prep_version and their tables do not move.
  *
  * Conventions as in michigan_hip.h: every call returns MG_OK or an MG_ERR_* code with a message behind mg_last_error(); arguments are
  * validated before the device is touched; all work is enqueued on `stream` (a hipStream_t) and nothing synchronises. */
@@ -19,14 +14,10 @@
 extern "C" {
 #endif
 
-#define MG_EDIT_STROKE 1                   /* what mg_edit_version() returns */
-
 #define MG_STROKE_FILTERS 32               /* bank [32][17][17], rgb_table [32][3] */
 #define MG_STROKE_RADIUS 8                 /* a filter is bank[k][-8 .. 8][-8 .. 8] */
 #define MG_STROKE_TILE_H 16                /* output pixels one workgroup owns; a tile without a stroke pixel is not filtered */
 #define MG_STROKE_TILE_W 16                /* (tests sit on these edges) */
-
-int mg_edit_version(void);
 
 /* stroke [n][h][w] u8 (non-zero = stroke), bank fp32 [32][17][17] (ops.dog_bank), rgb_table u8 [32][3] from the host
  * (ops.stroke_rgb_table: the kernel evaluates no sin or cos).  In float64, with s = stroke != 0:

@@ -1,11 +1,6 @@
-/* michigan_hip/feature_losses.h -- extension group of libmichigan_hip: the style and content terms of the generator objective as
+/* michigan_hip/feature_losses.h -- part of the C ABI of libmichigan_hip (michigan_hip.h includes it): the style and content terms of the generator objective as
  * fused VGG feature-moment kernels (mg_feat_moments.hip).  Reference: StyleContentLoss, models/networks/loss.py:624-711, called at
  * models/pix2pix_model.py:309-319.
- *
- * An EXTENSION GROUP is a set of entry points beside the core table of michigan_hip.h with the same three obligations: every mg_*(
- * declared here is mirrored in michigan_amd/_cabi.py (_EXT_PROTOS / EXTENSION_SYMBOLS), exported by the library, and -- where it writes
- * device memory -- has a guarded case in tests/test_gpu_style_guard_bands.py (tests/test_cabi_extensions.py holds the group to this).
- * It has a version of its own (mg_ext_version); MG_ABI_VERSION and the core table do not move when a group is added.
  *
  * Conventions as in michigan_hip.h: every call returns MG_OK or an MG_ERR_* code with a message behind mg_last_error(); arguments are
  * validated before the device is touched; all work is enqueued on `stream` (a hipStream_t) and nothing synchronises. */
@@ -17,8 +12,6 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-
-#define MG_EXT_FEATURE_LOSSES 1            /* what mg_ext_version() returns */
 
 #define MG_FEAT_STYLE   1                  /* `flags` bit 0 */
 #define MG_FEAT_CONTENT 2                  /* `flags` bit 1 */
@@ -68,7 +61,6 @@ typedef struct mg_feat_moment_desc {
     void* ws;
 } mg_feat_moment_desc;
 
-int mg_ext_version(void);
 /* bytes of `ws` for either dtype; 0 for a geometry the entry points refuse */
 int64_t mg_feat_moment_workspace(int32_t N, int64_t P, int32_t C);
 int mg_feat_moment_loss_fwd(const mg_feat_moment_desc* d, void* stream);

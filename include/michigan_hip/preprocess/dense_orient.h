@@ -1,13 +1,8 @@
-/* michigan_hip/preprocess/dense_orient.h -- preprocessing group of libmichigan_hip: the second half of dense hair-orientation
+/* michigan_hip/preprocess/dense_orient.h -- part of the C ABI of libmichigan_hip (michigan_hip.h includes it): the second half of dense hair-orientation
  * extraction (mg_orient_smooth.hip).  Reference: cal_orientation.py:101-109 -- the flow field of the arg-max orientation, two
  * cv2.GaussianBlur(sigma 4) calls, atan2 and the quantisation to the uint8 map the data set stores.  The first half (gray image,
  * 32 difference-of-Gaussians filters, first arg-max; cal_orientation.py:60-80) is mg_gabor_argmax_fwd of michigan_hip.h with the bank
  * of ops.dog_bank().
- *
- * A PREPROCESSING GROUP is an extension group (see michigan_hip/feature_losses.h) one directory down: every mg_*( declared under
- * michigan_hip/preprocess/ is mirrored in michigan_amd/_cabi.py (_PREP_PROTOS / PREPROCESS_SYMBOLS), exported by the library, and --
- * where it writes device memory -- has a guarded case in tests/test_gpu_dense_orient.py (tests/test_dense_orient.py holds the group to
- * this).  It has a version of its own (mg_prep_version); MG_ABI_VERSION, mg_ext_version and their tables do not move.
  *
  * Conventions as in michigan_hip.h: every call returns MG_OK or an MG_ERR_* code with a message behind mg_last_error(); arguments are
  * validated before the device is touched; all work is enqueued on `stream` (a hipStream_t) and nothing synchronises. */
@@ -19,8 +14,6 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-
-#define MG_PREP_DENSE_ORIENT 1             /* what mg_prep_version() returns */
 
 #define MG_ORIENT_RADIUS 16                /* taps[33] = taps[-16 .. 16] */
 #define MG_ORIENT_TILE_H 32                /* output pixels one workgroup owns (tests sit on these edges) */
@@ -38,7 +31,6 @@ extern "C" {
  *   orient_u8 [n][h][w] u8   = trunc(min(theta 255 / pi m, 255))
  * h, w >= 17: one reflection reaches every tap.  One launch, no intermediate in device memory, no atomics: two runs are
  * bit-identical.  n h w < 2^31. */
-int mg_prep_version(void);
 int mg_orient_smooth(const float* conf, const uint8_t* idx, const uint8_t* mask, const float* trig, const float* taps,
                      uint8_t* orient_u8, float* angle, int32_t n, int32_t h, int32_t w, void* stream);
 

@@ -1,6 +1,6 @@
 """ctypes binding of libmichigan_hip.so -- the ONLY route from Python to the GPU kernels.
 
-Mirrors include/michigan_hip.h one to one (struct layouts are checked against
+Mirrors include/michigan_hip.h and the headers it includes one to one (struct layouts are checked against
 ``mg_sizeof_desc`` at load time).  There is deliberately no CPU or eager-PyTorch
 fallback here: if the shared library is missing or a call fails, the caller gets
 a RuntimeError.  The test-suite may swap the backend object (``set_backend``) for
@@ -16,11 +16,8 @@ MG_F32, MG_BF16 = 0, 1
 MG_ACT_NONE, MG_ACT_RELU, MG_ACT_LRELU, MG_ACT_TANH = 0, 1, 2, 3
 MG_EPI_PLAIN, MG_EPI_SPADE = 0, 1
 MG_MAX_TAPS = 64
-MG_ABI_VERSION = 9
+MG_ABI_VERSION = 10
 MG_COMM_ID_BYTES = 128
-MG_EXT_FEATURE_LOSSES = 1                  # include/michigan_hip/feature_losses.h: what mg_ext_version() returns
-MG_PREP_DENSE_ORIENT = 1                   # include/michigan_hip/preprocess/dense_orient.h: what mg_prep_version() returns
-MG_EDIT_STROKE = 1                         # include/michigan_hip/editing/stroke_orient.h: what mg_edit_version() returns
 
 # enum mg_option (include/michigan_hip.h): the tuning switches of mg_set_option / mg_get_option; OPT_PROBE_* exist in -DMG_PROBES=1 builds only
 OPT_CONV_BIGTILES, OPT_CONV_HALO, OPT_WGRAD3X3, OPT_CONV_HALO_BIG, OPT_CONV_SPLITK, OPT_CONV_THIN, OPT_CONV_WIDE, OPT_CONV_DOT = 1, 2, 3, 4, 5, 6, 7, 8
@@ -187,36 +184,25 @@ _PROTOS = {
     "mg_sizeof_desc": ([_i32], _i32),
     "mg_abi_version": ([], _i32),
     "mg_last_error": ([], ctypes.c_char_p),
-}
-EXPORTED_SYMBOLS = tuple(_PROTOS)
-# The extension groups (include/michigan_hip/*.h): entry points beside the core table with the same obligations -- mirrored here, exported
-# by the library, guarded where they write device memory (tests/test_cabi_extensions.py).  Folding the two tables into one is a later
-# change: it moves MG_ABI_VERSION and the ledger tests that pin the core table.
-_EXT_PROTOS = {
-    "mg_ext_version": ([], _i32),
+    # include/michigan_hip/feature_losses.h
     "mg_feat_moment_workspace": ([_i32, _i64, _i32], _i64),
     "mg_feat_moment_loss_fwd": ([ctypes.POINTER(FeatMomentDesc), _vp], _i32),
     "mg_feat_moment_loss_bwd": ([ctypes.POINTER(FeatMomentDesc), _vp, _vp, _vp, _vp], _i32),
-}
-EXTENSION_SYMBOLS = tuple(_EXT_PROTOS)
-# The preprocessing group (include/michigan_hip/preprocess/*.h): a third table with the same obligations (tests/test_dense_orient.py).  It is
-# a table of its own because tests/test_cabi_extensions.py ties every device-writing name of _EXT_PROTOS to a guarded case in ONE test file.
-_PREP_PROTOS = {
-    "mg_prep_version": ([], _i32),
+    # include/michigan_hip/preprocess/dense_orient.h
     "mg_orient_smooth": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp], _i32),
-}
-PREPROCESS_SYMBOLS = tuple(_PREP_PROTOS)
-# The editing group (include/michigan_hip/editing/*.h): the stroke route of the interactive demo, a fourth table for the same reason
-# (tests/test_stroke.py holds it to the obligations; its guarded cases live in tests/test_gpu_stroke.py).
-_EDIT_PROTOS = {
-    "mg_edit_version": ([], _i32),
+    # include/michigan_hip/editing/stroke_orient.h
     "mg_stroke_orient": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp], _i32),
     "mg_stroke_compose": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
     "mg_inpaint_finish": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp], _i32),
 }
-EDITING_SYMBOLS = tuple(_EDIT_PROTOS)
+EXPORTED_SYMBOLS = tuple(_PROTOS)              # the whole ABI: tests/test_cabi_host.py holds it to the headers and to the library's exports
 _NO_STATUS = {"mg_wgrad_det_workspace", "mg_norm_apply2_supported", "mg_grad_slot_blocks", "mg_pack_job_blocks", "mg_sn_layer_blocks", "mg_stats_workspace", "mg_sizeof_desc", "mg_abi_version", "mg_last_error", "mg_noise_field_len", "mg_bicubic_ksize",
-              "mg_ext_version", "mg_feat_moment_workspace", "mg_prep_version", "mg_edit_version"}
+              "mg_feat_moment_workspace"}
+# entry points that take their descriptor by reference: the first argument is a pointer to one of the Structure mirrors above
+_BY_REF = {fn for fn, (argtypes, _) in _PROTOS.items()
+           if argtypes and isinstance(getattr(argtypes[0], "_type_", None), type) and issubclass(argtypes[0]._type_, ctypes.Structure)}
+# mg_sizeof_desc(which) -> the mirror it must agree with
+DESC_MIRRORS = (ConvDesc, WgradDesc, GradSlot, PackJob, SnLayer, NormApply2Desc, PyramidDesc, FeatMomentDesc)
 
 LIB_PATH = os.environ.get("MG_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmichigan_hip.so")   # MG_LIB: a measurement variant (tools/build_variant.py)
 
@@ -241,31 +227,21 @@ class HipBackend:
         # torch must already have loaded its libamdhip64 so that we bind to the same runtime.
         import torch  # noqa: F401
         self._lib = ctypes.CDLL(path)
-        for table in (_PROTOS, _EXT_PROTOS, _PREP_PROTOS, _EDIT_PROTOS):
-            for fn, (argtypes, restype) in table.items():
-                f = getattr(self._lib, fn)          # AttributeError if a symbol is missing
-                f.argtypes, f.restype = argtypes, restype
+        for fn, (argtypes, restype) in _PROTOS.items():
+            f = getattr(self._lib, fn)          # AttributeError if a symbol is missing
+            f.argtypes, f.restype = argtypes, restype
         if self._lib.mg_abi_version() != MG_ABI_VERSION:
             raise RuntimeError("libmichigan_hip.so ABI version mismatch")
-        if self._lib.mg_ext_version() != MG_EXT_FEATURE_LOSSES:
-            raise RuntimeError("libmichigan_hip.so extension-group version mismatch (michigan_hip/feature_losses.h)")
-        if self._lib.mg_prep_version() != MG_PREP_DENSE_ORIENT:
-            raise RuntimeError("libmichigan_hip.so preprocessing-group version mismatch (michigan_hip/preprocess/dense_orient.h)")
-        if self._lib.mg_edit_version() != MG_EDIT_STROKE:
-            raise RuntimeError("libmichigan_hip.so editing-group version mismatch (michigan_hip/editing/stroke_orient.h)")
-        if (self._lib.mg_sizeof_desc(0) != ctypes.sizeof(ConvDesc) or self._lib.mg_sizeof_desc(1) != ctypes.sizeof(WgradDesc)
-                or self._lib.mg_sizeof_desc(2) != ctypes.sizeof(GradSlot) or self._lib.mg_sizeof_desc(3) != ctypes.sizeof(PackJob)
-                or self._lib.mg_sizeof_desc(4) != ctypes.sizeof(SnLayer) or self._lib.mg_sizeof_desc(5) != ctypes.sizeof(NormApply2Desc)
-                or self._lib.mg_sizeof_desc(6) != ctypes.sizeof(PyramidDesc)):
+        if any(self._lib.mg_sizeof_desc(which) != ctypes.sizeof(mirror) for which, mirror in enumerate(DESC_MIRRORS)):
             raise RuntimeError("ctypes mirror of the descriptor structs is out of sync with include/michigan_hip.h")
 
     def __getattr__(self, fn):
-        if fn not in _PROTOS and fn not in _EXT_PROTOS and fn not in _PREP_PROTOS and fn not in _EDIT_PROTOS:
+        if fn not in _PROTOS:
             raise AttributeError(fn)
         raw = getattr(self._lib, fn)
         if fn in _NO_STATUS:
             return raw
-        by_ref = fn in ("mg_conv_taps", "mg_conv_wgrad", "mg_norm_bwd_apply2", "mg_nearest_pyramid", "mg_feat_moment_loss_fwd", "mg_feat_moment_loss_bwd")
+        by_ref = fn in _BY_REF
 
         def call(*args):
             if by_ref:

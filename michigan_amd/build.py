@@ -35,15 +35,17 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (looked at $HIPCC, /opt/rocm/bin/hipcc, PATH)")
 
 
+def _public_headers() -> list:
+    """Every file under include/, sub-folders included, in a fixed order."""
+    return sorted(os.path.join(d, f) for d, _, files in os.walk(INCLUDE) for f in files)
+
+
 def _fingerprint(src: str = "") -> str:
     """Hash of the flags, every header, and either one translation unit (`src`) or all of them."""
     h = hashlib.sha256()
     h.update(" ".join(CXXFLAGS).encode())
     paths = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h") or (not src and f.endswith(".hip"))]
-    paths += [os.path.join(INCLUDE, f) for f in sorted(os.listdir(INCLUDE))]
-    paths += [os.path.join(INCLUDE, "michigan_hip", f) for f in sorted(os.listdir(os.path.join(INCLUDE, "michigan_hip")))]   # the extension groups
-    paths += [os.path.join(INCLUDE, "michigan_hip", "preprocess", f) for f in sorted(os.listdir(os.path.join(INCLUDE, "michigan_hip", "preprocess")))]
-    paths += [os.path.join(INCLUDE, "michigan_hip", "editing", f) for f in sorted(os.listdir(os.path.join(INCLUDE, "michigan_hip", "editing")))]
+    paths += _public_headers()
     if src:
         paths.append(os.path.join(CSRC, src))
     for p in paths:
@@ -59,12 +61,11 @@ def source_hash() -> str:
     same sources (profiles/*_conv_traffic.json is stamped with it; bench.py compares)."""
     h = hashlib.sha256()
     h.update(" ".join(f for f in CXXFLAGS if not f.startswith("-I")).encode())
-    for d in (CSRC, INCLUDE):
-        for f in sorted(os.listdir(d)):
-            if f.endswith((".h", ".hip")):
-                h.update(f.encode())
-                with open(os.path.join(d, f), "rb") as fh:
-                    h.update(fh.read())
+    for p in [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + _public_headers():
+        if p.endswith((".h", ".hip")):
+            h.update(os.path.relpath(p, REPO_ROOT).replace(os.sep, "/").encode())
+            with open(p, "rb") as fh:
+                h.update(fh.read())
     return h.hexdigest()[:16]
 
 

@@ -439,8 +439,6 @@ int fm_check(const char* name, const mg_feat_moment_desc* d, FmArgs& a, FmGeom& 
 
 }  // namespace
 
-extern "C" int mg_ext_version(void) { return MG_EXT_FEATURE_LOSSES; }
-
 extern "C" int64_t mg_feat_moment_workspace(int32_t N, int64_t P, int32_t C)
 {
     if (N <= 0 || N > 65535 || P <= 0 || P >= ((int64_t)1 << 31) || C <= 0 || C % 4) return 0;

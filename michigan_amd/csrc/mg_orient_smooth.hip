@@ -131,8 +131,6 @@ __global__ __launch_bounds__(NTHREADS) void orient_smooth_kernel(const float* __
 
 }  // namespace
 
-extern "C" int mg_prep_version(void) { return MG_PREP_DENSE_ORIENT; }
-
 extern "C" int mg_orient_smooth(const float* conf, const uint8_t* idx, const uint8_t* mask, const float* trig, const float* taps,
                                 uint8_t* orient_u8, float* angle, int32_t n, int32_t h, int32_t w, void* stream)
 {

@@ -192,8 +192,6 @@ inline unsigned stream_grid(int64_t total) { return (unsigned)std::min<int64_t>(
 
 }  // namespace
 
-extern "C" int mg_edit_version(void) { return MG_EDIT_STROKE; }
-
 extern "C" int mg_stroke_orient(const uint8_t* stroke, const float* bank, const uint8_t* rgb_table, uint8_t* rgb_u8, uint8_t* idx, float* conf,
                                 int32_t n, int32_t h, int32_t w, void* stream)
 {

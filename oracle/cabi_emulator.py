@@ -20,6 +20,8 @@ import math
 
 import torch
 
+from oracle import contracts as K
+
 MG_F32, MG_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 _TD = {MG_F32: torch.float32, MG_BF16: torch.bfloat16}
@@ -78,7 +80,26 @@ def _gather(x, hj, wj, isy, isx, dy, dx):
 
 
 class EmulatorBackend:
+    """Every entry point of michigan_amd._cabi.EXPORTED_SYMBOLS except the collectives (mg_comm_*, mg_allreduce_*) and the probes
+    (tests/test_cabi_host.py holds it to that).  `calls` is the log of the entry points whose launches the tests count: (name, flags
+    or None) in call order, noted before anything is checked, so a refused call is in it too."""
     name = "emulator"
+
+    def __init__(self):
+        self.calls = []
+
+    def _note(self, fn, flags=None):
+        self.calls.append((fn, flags))
+
+    def count(self, fn):
+        return sum(1 for name, _ in self.calls if name == fn)
+
+    def flags(self, fn):
+        return [fl for name, fl in self.calls if name == fn]
+
+    @staticmethod
+    def _fail(fn, msg):
+        raise RuntimeError("%s failed (code 1): %s: %s" % (fn, fn, msg))
 
     # -- bookkeeping ---------------------------------------------------------
     def mg_abi_version(self):
@@ -90,7 +111,7 @@ class EmulatorBackend:
 
     def mg_sizeof_desc(self, which):
         from michigan_amd import _cabi
-        return ctypes.sizeof((_cabi.ConvDesc, _cabi.WgradDesc, _cabi.GradSlot, _cabi.PackJob, _cabi.SnLayer, _cabi.NormApply2Desc, _cabi.PyramidDesc)[which])
+        return ctypes.sizeof(_cabi.DESC_MIRRORS[which])
 
     def mg_last_error(self):
         return b""
@@ -567,6 +588,7 @@ class EmulatorBackend:
         return 0.299 * x[..., 0] + 0.587 * x[..., 1] + 0.144 * x[..., 2]           # [N,H,W]
 
     def mg_gabor_argmax_fwd(self, img, bank, conf, idx, dtype, N, H, W, C, stream=None):
+        self._note("mg_gabor_argmax_fwd")
         import torch.nn.functional as F
         g = self._gray(_view(img, (N, H, W, C), _TD[dtype]))[:, None]
         k = _view(bank, (32, 1, 17, 17), torch.float32).double()
@@ -845,4 +867,213 @@ class EmulatorBackend:
         d = _view(dst, (N, Hd, Wd, C), torch.uint8)
         for n in range(N):
             d[n] = torch.from_numpy(IO.pil_bicubic_resize_u8(s[n], Hd, Wd))
+        return 0
+
+    # ---- image-space colour losses (mg_color_loss.hip, mg_hair_lab.hip): the arithmetic is oracle/contracts.py ---------------------
+
+    def _color_inputs(self, img, real, real_nstride, back, back_nstride, dtype, N, H, W, C, flags):
+        assert 1 <= flags <= 7 and C >= 3
+        x = _view(img, (N, H, W, C), _TD[dtype]).double()[..., :3].permute(0, 3, 1, 2)
+        base = _view(real, ((N - 1) * real_nstride + 3 * H * W,), torch.float32)
+        r = torch.as_strided(base, (N, 3, H, W), (real_nstride, H * W, W, 1)).double()
+        m = self._plane(back, N, back_nstride, H, W).double() if flags & K.COLOR_BACKGROUND else None
+        return x, r, m
+
+    def mg_color_loss_fwd(self, img, real, real_nstride, back, back_nstride, dtype, N, H, W, C, flags, out, ws, stream=None):
+        self._note("mg_color_loss_fwd", flags)
+        x, r, m = self._color_inputs(img, real, real_nstride, back, back_nstride, dtype, N, H, W, C, flags)
+        _view(out, (3,), torch.float32)[:] = K.color_terms(x, r, m, flags)[0].float()
+        return 0
+
+    def mg_color_loss_bwd(self, img, real, real_nstride, back, back_nstride, g_lab, g_rgb, g_back, dtype, N, H, W, C, flags, dimg, stream=None):
+        self._note("mg_color_loss_bwd", flags)
+        x, r, m = self._color_inputs(img, real, real_nstride, back, back_nstride, dtype, N, H, W, C, flags)
+        g = [float(_view(p, (1,), torch.float32)[0]) if _addr(p) else 0.0 for p in (g_lab, g_rgb, g_back)]
+        grad = K.color_terms(x, r, m, flags, g)[1]
+        d = _view(dimg, (N, H, W, C), _TD[dtype])
+        d.zero_()
+        d[..., :3] = grad.permute(0, 2, 3, 1).to(_TD[dtype])
+        return 0
+
+    @staticmethod
+    def _image(ptr, nstride, N, H, W):
+        base = _view(ptr, ((N - 1) * nstride + 3 * H * W,), torch.float32)
+        return torch.as_strided(base, (N, 3, H, W), (nstride, H * W, W, 1)).double()
+
+    def _hair_inputs(self, img, ref, ref_nstride, hair_tag, hair_tag_nstride, hair_ref, hair_ref_nstride, tgt, tgt_nstride, back, back_nstride,
+                     dtype, N, H, W, C, flags):
+        assert 1 <= flags <= 3 and C >= 3
+        x = _view(img, (N, H, W, C), _TD[dtype]).double()[..., :3].permute(0, 3, 1, 2)
+        r = mf = mr = t = mb = None
+        if flags & K.HAIR_LAB:
+            mf = self._plane(hair_tag, N, hair_tag_nstride, H, W).double()
+            if _addr(ref):                                               # the backward does not get ref / hair_ref
+                r, mr = self._image(ref, ref_nstride, N, H, W), self._plane(hair_ref, N, hair_ref_nstride, H, W).double()
+        if flags & K.HAIR_BACKGROUND:
+            t, mb = self._image(tgt, tgt_nstride, N, H, W), self._plane(back, N, back_nstride, H, W).double()
+        return x, r, mf, mr, t, mb
+
+    def mg_hair_lab_fwd(self, img, ref, ref_nstride, hair_tag, hair_tag_nstride, hair_ref, hair_ref_nstride, tgt, tgt_nstride, back, back_nstride,
+                        dtype, N, H, W, C, flags, out, stats, ws, stream=None):
+        self._note("mg_hair_lab_fwd", flags)
+        x, r, mf, mr, t, mb = self._hair_inputs(img, ref, ref_nstride, hair_tag, hair_tag_nstride, hair_ref, hair_ref_nstride, tgt, tgt_nstride,
+                                                back, back_nstride, dtype, N, H, W, C, flags)
+        losses, _, (da, db) = K.hair_terms(x, r, mf, mr, t, mb, flags)
+        _view(out, (2,), torch.float32)[:] = losses.float()
+        if flags & K.HAIR_LAB:
+            sf, sr = mf.sum(dim=(1, 2)), mr.sum(dim=(1, 2))
+            inv = lambda s: 1.0 / torch.where(s == 0, torch.ones_like(s), s)
+            _view(stats, (N, 4), torch.float32)[:] = torch.stack([da, db, inv(sf), inv(sr)], dim=1).float()
+        return 0
+
+    def mg_hair_lab_bwd(self, img, hair_tag, hair_tag_nstride, tgt, tgt_nstride, back, back_nstride, stats, g_hair, g_back,
+                        dtype, N, H, W, C, flags, dimg, stream=None):
+        """Uses what the kernel uses: the per-sample signs and 1 / S_f of `stats`, no second reduction."""
+        self._note("mg_hair_lab_bwd", flags)
+        x, _, mf, _, t, mb = self._hair_inputs(img, None, 0, hair_tag, hair_tag_nstride, None, 0, tgt, tgt_nstride, back, back_nstride,
+                                               dtype, N, H, W, C, flags)
+        g = [float(_view(p, (1,), torch.float32)[0]) if _addr(p) else 0.0 for p in (g_hair, g_back)]
+        grad = torch.zeros_like(x)
+        if flags & K.HAIR_LAB:
+            st = _view(stats, (N, 4), torch.float32).double()
+            xyz_f = K._xyz(x)
+            sa, sb = 500 * torch.sign(st[:, 0])[:, None, None], 200 * torch.sign(st[:, 1])[:, None, None]
+            dfx = K._df(xyz_f)
+            dxyz = torch.stack([sa * dfx[:, 0], (sb - sa) * dfx[:, 1], -sb * dfx[:, 2]], dim=1)
+            grad += g[0] / (2 * N) * 0.5 * (mf * st[:, 2][:, None, None]).unsqueeze(1) * torch.einsum("rc,nrhw->nchw", K.MN, dxyz)
+        if flags & K.HAIR_BACKGROUND:
+            grad += K.hair_terms(x, None, None, None, t, mb, K.HAIR_BACKGROUND, (0.0, g[1]))[1]
+        d = _view(dimg, (N, H, W, C), _TD[dtype])
+        d.zero_()
+        d[..., :3] = grad.permute(0, 2, 3, 1).to(_TD[dtype])
+        return 0
+
+    # ---- style and content (mg_feat_moments.hip) -----------------------------------------------------------------------------------
+    def mg_feat_moment_workspace(self, n, p, c):
+        return 64 if n > 0 and p > 0 and c > 0 and c % 4 == 0 else 0          # any positive size will do here; the library's layout is its own business
+
+    @staticmethod
+    def _feat(ptr, d):
+        v = _view(ptr, (d.N, d.P, d.C), _TD[d.dtype])
+        return None if v is None else v.double().permute(0, 2, 1)
+
+    @staticmethod
+    def _mask(ptr, nstride, d):
+        if not _addr(ptr):
+            return None
+        base = _view(ptr, ((d.N - 1) * nstride + d.P,), torch.float32)
+        return torch.as_strided(base, (d.N, d.P), (nstride, 1)).double()
+
+    def _operands(self, d):
+        assert 1 <= d.flags <= 3 and d.C % (8 if d.dtype == 1 else 4) == 0
+        st, co = d.flags & K.FEAT_STYLE, d.flags & K.FEAT_CONTENT
+        x = self._feat(d.x, d)
+        s = self._feat(d.s, d) if st else None
+        t = self._feat(d.t, d) if co else None
+        mx = self._mask(d.mask_x, d.mask_x_nstride, d) if st else None
+        ms = self._mask(d.mask_s, d.mask_s_nstride, d) if st else None
+        ml = self._mask(d.mask_t, d.mask_t_nstride, d) if co else None
+        assert (mx is None) == (ms is None)
+        return x, s, t, mx, ms, ml
+
+    def mg_feat_moment_loss_fwd(self, d, stream=None):
+        self._note("mg_feat_moment_loss_fwd", d.flags)
+        x, s, t, mx, ms, ml = self._operands(d)
+        out = _view(d.out, (2,), torch.float32)
+        coef = _view(d.coef, (d.N, d.C, 4), torch.float32)
+        out.zero_()
+        coef.zero_()
+        if d.flags & K.FEAT_STYLE:
+            style, a, b, mu_x = K.coefficients(x, s, mx, ms)
+            out[0] = float(style)
+            coef[..., 0], coef[..., 1], coef[..., 2] = a.float(), b.float(), mu_x.float()
+        if d.flags & K.FEAT_CONTENT:
+            den = K.content_den(d.N, d.C, d.P, ml)
+            diff = x - t if ml is None else ml.unsqueeze(1) * (K._kept(x, ml) - K._kept(t, ml))
+            out[1] = float((diff ** 2).sum() / den)
+            coef[..., 3] = 2.0 / den
+        return 0
+
+    def mg_feat_moment_loss_bwd(self, d, g_style, g_content, dx, stream=None):
+        """Uses what the kernel uses: the fp32 table of the forward, no second reduction."""
+        self._note("mg_feat_moment_loss_bwd", d.flags)
+        x = self._feat(d.x, d)
+        gs, gc = [float(_view(p, (1,), torch.float32)[0]) if _addr(p) else 0.0 for p in (g_style, g_content)]
+        gs, gc = (gs if d.flags & K.FEAT_STYLE else 0.0), (gc if d.flags & K.FEAT_CONTENT else 0.0)
+        coef = _view(d.coef, (d.N, d.C, 4), torch.float32).double()
+        mx = self._mask(d.mask_x, d.mask_x_nstride, d) if gs else None
+        ml = self._mask(d.mask_t, d.mask_t_nstride, d) if gc else None
+        t = self._feat(d.t, d) if gc else None
+        den = 2.0 / float(coef[0, 0, 3]) if gc else 1.0
+        grad = K.gradient(x, t, mx, ml, coef[..., 0], coef[..., 1], coef[..., 2], den, gs, gc)
+        _view(dx, (d.N, d.P, d.C), _TD[d.dtype])[:] = grad.permute(0, 2, 1).to(_TD[d.dtype])
+        return 0
+
+    # ---- dense orientation, second half (mg_orient_smooth.hip) -----------------------------------------------------------------------
+    def mg_orient_smooth(self, conf, idx, mask, trig, taps, orient_u8, angle, n, h, w, stream=None):
+        self._note("mg_orient_smooth")
+        if not (_addr(conf) and _addr(idx) and _addr(mask) and _addr(trig) and _addr(taps) and _addr(orient_u8)):
+            self._fail("mg_orient_smooth", "null pointer")
+        if n < 1 or h <= K.ORIENT_RADIUS or w <= K.ORIENT_RADIUS:
+            self._fail("mg_orient_smooth", "bad geometry")
+        res = K.smooth_contract(_view(conf, (n, h, w), torch.float32).numpy(), _view(idx, (n, h, w), torch.uint8).numpy() & 31,
+                              _view(mask, (n, h, w), torch.uint8).numpy(), _view(trig, (32, 2), torch.float32).numpy(),
+                              _view(taps, (2 * K.ORIENT_RADIUS + 1,), torch.float32).numpy())
+        _view(orient_u8, (n, h, w), torch.uint8)[:] = torch.from_numpy(res["u8"])
+        if _addr(angle):
+            _view(angle, (n, h, w), torch.float32)[:] = torch.from_numpy(res["theta"]).float()
+        return 0
+
+    # ---- stroke editing (mg_stroke.hip) ------------------------------------------------------------------------------------------------
+    def mg_stroke_orient(self, stroke, bank, rgb_table, rgb_u8, idx, conf, n, h, w, stream=None):
+        self._note("mg_stroke_orient")
+        if not (_addr(stroke) and _addr(bank) and _addr(rgb_table) and _addr(rgb_u8)):
+            self._fail("mg_stroke_orient", "null pointer")
+        if n < 1 or h < 1 or w < 1:
+            self._fail("mg_stroke_orient", "bad geometry")
+        res = K.stroke_contract(_view(stroke, (n, h, w), torch.uint8).numpy(), _view(bank, (32, 17, 17), torch.float32).numpy(),
+                              _view(rgb_table, (32, 3), torch.uint8).numpy())
+        _view(rgb_u8, (n, h, w, 3), torch.uint8)[:] = torch.from_numpy(res["rgb"])
+        if _addr(idx):
+            _view(idx, (n, h, w), torch.uint8)[:] = torch.from_numpy(res["idx"])
+        if _addr(conf):
+            _view(conf, (n, h, w), torch.float32)[:] = torch.from_numpy(res["conf"]).float()
+        return 0
+
+    @staticmethod
+    def _tables(fn, ytab, xtab, ny, nx, sy, sx):
+        if (not _addr(ytab) and ny != sy) or (not _addr(xtab) and nx != sx):
+            EmulatorBackend._fail(fn, "a null table is the identity")
+        return (_view(ytab, (ny,), torch.int32).clamp(0, sy - 1) if _addr(ytab) else None,
+                _view(xtab, (nx,), torch.int32).clamp(0, sx - 1) if _addr(xtab) else None)
+
+    def mg_stroke_compose(self, orient_rgb, noise, hole, stroke, stroke_mask, ytab, xtab, dtype, n, h, w, ho, wo, inp, stream=None):
+        self._note("mg_stroke_compose")
+        if not (_addr(orient_rgb) and _addr(noise) and _addr(hole) and _addr(inp)):
+            self._fail("mg_stroke_compose", "null pointer")
+        if bool(_addr(stroke)) != bool(_addr(stroke_mask)):
+            self._fail("mg_stroke_compose", "stroke and stroke_mask are given together or not at all")
+        if dtype not in (0, 1):
+            self._fail("mg_stroke_compose", "bad dtype")
+        if min(n, h, w, ho, wo) < 1:
+            self._fail("mg_stroke_compose", "bad geometry")
+        yt, xt = self._tables("mg_stroke_compose", ytab, xtab, ho, wo, h, w)
+        td = torch.bfloat16 if dtype == 1 else torch.float32
+        v3, v1 = lambda p: _view(p, (n, 3, h, w), torch.float32), lambda p: _view(p, (n, 1, h, w), torch.float32)
+        res = K.compose_contract(v3(orient_rgb), v3(noise), v1(hole), v3(stroke) if _addr(stroke) else None,
+                               v1(stroke_mask) if _addr(stroke_mask) else None, yt, xt, td)
+        _view(inp, (n, ho, wo, 8), td)[:] = res
+        return 0
+
+    def mg_inpaint_finish(self, net_out, ytab, xtab, hole, orient_rgb, mask, n, h, w, ho, wo, out_rgb, orient2, stream=None):
+        self._note("mg_inpaint_finish")
+        if not (_addr(net_out) and _addr(hole) and _addr(orient_rgb) and _addr(mask) and _addr(out_rgb) and _addr(orient2)):
+            self._fail("mg_inpaint_finish", "null pointer")
+        if min(n, h, w, ho, wo) < 1:
+            self._fail("mg_inpaint_finish", "bad geometry")
+        yt, xt = self._tables("mg_inpaint_finish", ytab, xtab, h, w, ho, wo)
+        out, o2 = K.finish_contract(_view(net_out, (n, 3, ho, wo), torch.float32), yt, xt, _view(hole, (n, 1, h, w), torch.float32),
+                                  _view(orient_rgb, (n, 3, h, w), torch.float32), _view(mask, (n, 1, h, w), torch.float32))
+        _view(out_rgb, (n, 3, h, w), torch.float32)[:] = out
+        _view(orient2, (n, 2, h, w), torch.float32)[:] = o2
         return 0

@@ -1,52 +1,21 @@
-"""TEST INFRASTRUCTURE ONLY -- the float64 contract of mg_orient_smooth (include/michigan_hip/preprocess/dense_orient.h) on plain
-arrays (`smooth_contract`, with the switches the mutants of tests/test_dense_orient.py flip) and on top of the C-ABI contract
-emulator (`DenseOrientEmulator`: StyleLossEmulator + the preprocessing group, counting its calls), the comparison rule for level
-maps (`rule2`), the seeded strand images of tests/golden/dense_orient_i.npz (`make_sets`: the fixtures hold only what the
-reference computed on them), the fixture loaders and `kernel_geometry`, the mirror of the kernel's tiling.
-
-Works on host memory through the raw pointers the kernel gets, computes in float64 and rounds once at the outputs.
-The product never imports it.
+"""TEST INFRASTRUCTURE ONLY -- fixtures of the dense-orientation tests: the comparison rule for level maps (`rule2`, `compared`,
+`circular`), the seeded strand images of tests/golden/dense_orient_i.npz (`make_sets`: the fixtures hold only what the reference
+computed on them), the fixture loader, the float64 contract run over a fixture with one thing broken (`contract_on_fixture`,
+`MUTANTS`) and `kernel_geometry`, the mirror of the kernel's tiling.  The contract itself is oracle/contracts.smooth_contract.
 """
 import math
 import os
-import re
 
 import numpy as np
 import torch
 
-from oracle.cabi_emulator import _addr, _view
-from style_loss_emulator import GOLDEN, StyleLossEmulator
+from oracle.contracts import ORIENT_RADIUS as RADIUS, argmax_contract, smooth_contract
+from parity_utils import GOLDEN
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RADIUS = 16
 MIN_REL_MAGNITUDE = 1e-3                 # pixels whose oracle flow magnitude is below this share of the in-mask maximum are not compared
 MAX_EXCLUDED = 0.005
 SYNTHETIC_SHAPES = ((17, 17), (33, 47), (70, 95))
 CROP = (206, 72, 128)                    # set ii: row, column, side of the crop of sample 67172
-
-
-# ---- the contract ------------------------------------------------------------------------------------------------------------------------
-def smooth_contract(conf, idx, mask, trig, taps, reflect101=True, mask_multiply=True, truncate=True):
-    """conf / idx / mask [N,H,W] arrays, trig [32,2], taps [2r+1] -> dict(theta, level (float64 [N,H,W]), u8, bx, by).  The three
-    switches are the contract as written; a mutant turns one off."""
-    conf, trig, taps = np.asarray(conf, np.float64), np.asarray(trig, np.float64), np.asarray(taps, np.float64)
-    idx, m = np.asarray(idx).astype(np.int64), np.asarray(mask) != 0
-    r = (len(taps) - 1) // 2
-    n, h, w = conf.shape
-    assert h > r and w > r
-    c = np.where(m, conf, 0.0)                                            # conf is not read as a number where the mask is 0
-    out = []
-    for f in (trig[idx, 0] * c, trig[idx, 1] * c):
-        p = np.pad(f, ((0, 0), (r, r), (r, r)), mode="reflect" if reflect101 else "symmetric")
-        rows = sum(taps[k] * p[:, :, k:k + w] for k in range(2 * r + 1))
-        out.append(sum(taps[k] * rows[:, k:k + h, :] for k in range(2 * r + 1)))
-    bx, by = out
-    theta = 0.5 * np.arctan2(by, bx)
-    theta = np.where(theta < 0, theta + math.pi, theta)
-    level = theta * 255.0 / math.pi * (m if mask_multiply else 1.0)
-    level = np.minimum(level, 255.0)
-    u8 = (np.trunc(level) if truncate else np.minimum(np.round(level), 255.0)).astype(np.uint8)
-    return dict(theta=theta, level=level, u8=u8, bx=bx, by=by)
 
 
 def circular(a, b):
@@ -83,15 +52,6 @@ def rule2(got, fixture, angle_factor=8.0):
     return ok, fig
 
 
-def argmax_contract(image, bank):
-    """float64 contract of mg_gabor_argmax_fwd on plain tensors: image fp32 [N,H,W,3] in [-1, 1], bank [32,17,17] -> (conf, idx) arrays"""
-    import torch.nn.functional as F
-    x = (image[..., :3].double() + 1) / 2 * 255
-    g = (0.299 * x[..., 0] + 0.587 * x[..., 1] + 0.144 * x[..., 2])[:, None]
-    r = F.conv2d(g, bank.double().view(32, 1, 17, 17), padding=8).clamp_min(0)
-    return r.max(1)[0].numpy(), r.argmax(1).numpy()
-
-
 MUTANTS = ("edge_duplicating_reflection", "angle_step_pi_32", "taps_25", "no_mask_multiply", "bank_xy_swapped", "round_to_uint8")
 
 
@@ -116,37 +76,6 @@ def contract_on_fixture(fixture, mutant=None):
         out[geo] = smooth_contract(conf.astype(np.float32), idx, rec["mask"], trig, taps, reflect101=mutant != "edge_duplicating_reflection",
                                    mask_multiply=mutant != "no_mask_multiply", truncate=mutant != "round_to_uint8")
     return out
-
-
-# ---- on the C-ABI emulator -----------------------------------------------------------------------------------------------------------------
-class DenseOrientEmulator(StyleLossEmulator):
-    """StyleLossEmulator + the preprocessing group of michigan_hip/preprocess/dense_orient.h; counts the two launches of
-    inputs.dense_orientation (tests check: one call of each per batch)."""
-
-    def __init__(self):
-        super().__init__()
-        self.prep_calls = {"mg_gabor_argmax_fwd": 0, "mg_orient_smooth": 0}
-
-    def mg_prep_version(self):
-        return 1
-
-    def mg_gabor_argmax_fwd(self, *args, **kw):
-        self.prep_calls["mg_gabor_argmax_fwd"] += 1
-        return super().mg_gabor_argmax_fwd(*args, **kw)
-
-    def mg_orient_smooth(self, conf, idx, mask, trig, taps, orient_u8, angle, n, h, w, stream=None):
-        self.prep_calls["mg_orient_smooth"] += 1
-        if not (_addr(conf) and _addr(idx) and _addr(mask) and _addr(trig) and _addr(taps) and _addr(orient_u8)):
-            raise RuntimeError("mg_orient_smooth failed (code 1): mg_orient_smooth: null pointer")
-        if n < 1 or h <= RADIUS or w <= RADIUS:
-            raise RuntimeError("mg_orient_smooth failed (code 1): mg_orient_smooth: bad geometry")
-        res = smooth_contract(_view(conf, (n, h, w), torch.float32).numpy(), _view(idx, (n, h, w), torch.uint8).numpy() & 31,
-                              _view(mask, (n, h, w), torch.uint8).numpy(), _view(trig, (32, 2), torch.float32).numpy(),
-                              _view(taps, (2 * RADIUS + 1,), torch.float32).numpy())
-        _view(orient_u8, (n, h, w), torch.uint8)[:] = torch.from_numpy(res["u8"])
-        if _addr(angle):
-            _view(angle, (n, h, w), torch.float32)[:] = torch.from_numpy(res["theta"]).float()
-        return 0
 
 
 # ---- the inputs of the fixtures ----------------------------------------------------------------------------------------------------------
@@ -210,9 +139,3 @@ def kernel_geometry(n, h, w):
     kernel is compiled from, so a change of the tile that this mirror misses fails loudly instead of moving the cases off the edges."""
     ty, tx = -(-h // TILE_H), -(-w // TILE_W)
     return dict(tile_h=TILE_H, tile_w=TILE_W, tiles_y=ty, tiles_x=tx, blocks=n * ty * tx, patch_h=TILE_H + 2 * RADIUS, patch_w=TILE_W + 2 * RADIUS)
-
-
-def header_defines():
-    """{name: int} of the #defines of include/michigan_hip/preprocess/dense_orient.h"""
-    with open(os.path.join(ROOT, "include", "michigan_hip", "preprocess", "dense_orient.h")) as fh:
-        return {k: int(v) for k, v in re.findall(r"#define\s+(MG_[A-Z_]+)\s+(\d+)\b", fh.read())}

@@ -20,6 +20,36 @@ def golden(name):
     return np.load(os.path.join(GOLDEN, name))
 
 
+def load_tensors(name):
+    """tests/golden/<name> as {key: tensor}, scalars as Python numbers."""
+    z = golden(name)
+    return {k: (torch.from_numpy(z[k]) if z[k].ndim else z[k].item()) for k in z.files}
+
+
+class _Record(dict):
+    """dict with the `.files` of an NpzFile (what oracle.trainer_parity.compare iterates)."""
+    @property
+    def files(self):
+        return list(self)
+
+
+def load_trainer_golden(tag):
+    """trainer_<tag>.npz + trainer_<tag>_weights.npz for tag C (colour terms on), U (unpaired stage) or S (style and content on):
+    one record, split in two files to keep each under the size limit of a committed file."""
+    rec = {}
+    for fn in ("trainer_%s.npz" % tag, "trainer_%s_weights.npz" % tag):
+        with golden(fn) as z:
+            rec.update({k: z[k] for k in z.files})
+    return _Record(rec)
+
+
+def header_defines(path):
+    """{name: int} of the integer #defines of the header include/<path>"""
+    import re
+    with open(os.path.join(os.path.dirname(GOLDEN), os.pardir, "include", path)) as fh:
+        return {k: int(v) for k, v in re.findall(r"#define\s+(MG_[A-Z_]+)\s+(\d+)\b", fh.read())}
+
+
 def small_opt(**over):
     from michigan_amd.model import default_options
     cfg = load_cfg()

@@ -1,69 +1,21 @@
-"""TEST INFRASTRUCTURE ONLY -- the float64 contracts of the editing group (include/michigan_hip/editing/stroke_orient.h) on plain
-arrays (`stroke_contract` with the switches the mutants flip, `compose_contract`, `finish_contract`) and on top of the C-ABI contract
-emulator (`StrokeEmulator`: DenseOrientEmulator + the three entry points, counting their calls), the comparison rule of
-tests/test_stroke.py (`rule`), the seeded polyline masks of tests/golden/stroke_i.npz (`make_masks`: the fixture holds only what the
-reference computed on them), the fixture loader and `kernel_geometry`, the mirror of the kernel's tiling.
-
-Works on host memory through the raw pointers the kernels get.  The product never imports it.
+"""TEST INFRASTRUCTURE ONLY -- fixtures of the stroke-editing tests: the comparison rule of tests/test_stroke.py (`rule`), the seeded
+polyline masks of tests/golden/stroke_i.npz (`make_masks`: the fixture holds only what the reference computed on them), the seeded
+inputs of the glue entry points (`glue_inputs`), the fixture loader, the float64 contract run over a fixture with one thing broken
+(`contract_on_fixture`, `MUTANTS`) and `kernel_geometry`, the mirror of the kernel's tiling.  The contracts themselves are
+oracle/contracts.stroke_contract, compose_contract and finish_contract.
 """
 import os
-import re
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
-from dense_orient_emulator import DenseOrientEmulator
-from oracle.cabi_emulator import _addr, _view
-from style_loss_emulator import GOLDEN
+from oracle.contracts import STROKE_MUTANTS as MUTANTS, responses, stroke_contract
+from parity_utils import GOLDEN
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RADIUS = 8
 SHAPES = ((17, 17), (33, 47), (70, 95), (128, 128))
 WIDTHS = (1, 15)                         # the pen widths of the UI
 MAX_UNDECIDED = 0.10                     # share of stroke pixels whose float64 top-two gap is below tau
 TAU_FACTOR = 4.0                         # a 289-term fp32 sum taken in another order may err a few times more than ATen's
-MUTANTS = ("convolution", "bank_transposed", "argmax_before_clamp", "last_argmax", "rg_swapped", "outside_not_black", "reflected_border")
-
-
-# ---- the contract of mg_stroke_orient ------------------------------------------------------------------------------------------------
-def responses(stroke, bank, border="zero"):
-    """float64 [N,32,H,W]: resp_k[y,x] = sum_ij bank[k][i][j] s[y+i-8, x+j-8] with s = stroke != 0 (correlation)"""
-    s = torch.from_numpy((np.asarray(stroke) != 0).astype(np.float64))[:, None]
-    b = torch.as_tensor(np.asarray(bank), dtype=torch.float64).view(32, 1, 17, 17)
-    if border == "reflect":
-        n, _, h, w = s.shape
-        iy = np.pad(np.arange(h), RADIUS, mode="symmetric" if h <= RADIUS else "reflect")
-        ix = np.pad(np.arange(w), RADIUS, mode="symmetric" if w <= RADIUS else "reflect")
-        return F.conv2d(s[:, :, iy][:, :, :, ix], b).numpy()
-    return F.conv2d(s, b, padding=RADIUS).numpy()
-
-
-def stroke_contract(stroke, bank, rgb_table, mutant=None):
-    """stroke u8 [N,H,W], bank [32,17,17], rgb_table u8 [32,3] -> dict(rgb u8 [N,H,W,3], idx u8, conf float64, resp float64
-    [N,32,H,W]).  `mutant` (one of MUTANTS) breaks one thing the fixtures must notice."""
-    assert mutant is None or mutant in MUTANTS
-    bank, table = np.asarray(bank), np.asarray(rgb_table)
-    if mutant == "convolution":
-        bank = bank[:, ::-1, ::-1].copy()
-    if mutant == "bank_transposed":
-        bank = bank.transpose(0, 2, 1).copy()
-    if mutant == "rg_swapped":
-        table = table[:, [1, 0, 2]]
-    s = np.asarray(stroke) != 0
-    resp = responses(stroke, bank, border="reflect" if mutant == "reflected_border" else "zero")
-    clamped = np.maximum(resp, 0.0)
-    conf = clamped.max(axis=1)
-    if mutant == "argmax_before_clamp":
-        idx = resp.argmax(axis=1)
-    elif mutant == "last_argmax":
-        idx = 31 - clamped[:, ::-1].argmax(axis=1)
-    else:
-        idx = clamped.argmax(axis=1)                                       # numpy: the first maximum
-    rgb = table[idx]
-    if mutant != "outside_not_black":
-        rgb = np.where(s[..., None], rgb, 0)
-    return dict(rgb=rgb.astype(np.uint8), idx=np.where(s, idx, 0).astype(np.uint8), conf=np.where(s, conf, 0.0), resp=resp)
 
 
 def rule(got, fixture, max_undecided=MAX_UNDECIDED):
@@ -144,100 +96,6 @@ def contract_on_fixture(fixture, mutant=None):
     return {geo: stroke_contract(rec["mask"], fixture["bank"], ops.stroke_rgb_table().numpy(), mutant) for geo, rec in fixture["geometries"].items()}
 
 
-# ---- the contracts of the two glue entry points: fp32, one operation at a time ---------------------------------------------------------
-def _gather(t, ytab, xtab):
-    t = t if ytab is None else t[:, :, ytab.long()]
-    return t if xtab is None else t[:, :, :, xtab.long()]
-
-
-def compose_contract(orient_rgb, noise, hole, stroke, stroke_mask, ytab, xtab, dtype):
-    """fp32 torch tensors (NCHW) -> NHWC8 `dtype`; every product and sum is one fp32 torch operation, in the reference's order"""
-    o, nz, hl = (_gather(t, ytab, xtab) for t in (orient_rgb, noise, hole))
-    if stroke is not None:
-        st, sm = _gather(stroke, ytab, xtab), _gather(stroke_mask, ytab, xtab)
-        rgb = o * (1 - hl) + nz * (hl - sm) + st * sm
-    else:
-        sm = torch.zeros_like(hl)
-        rgb = o * (1 - hl) + nz * hl
-    z = torch.zeros_like(hl)
-    return torch.cat([rgb, hl, sm, z, z, z], dim=1).permute(0, 2, 3, 1).contiguous().to(dtype)
-
-
-def finish_contract(net_out, ytab, xtab, hole, orient_rgb, mask):
-    out = _gather(net_out, ytab, xtab) * hole + orient_rgb * (1 - hole)
-    o2 = (out[:, :-1] - 0.5) * 2
-    return out, torch.stack([o2[:, 1], o2[:, 0]], dim=1) * mask
-
-
-# ---- on the C-ABI emulator -----------------------------------------------------------------------------------------------------------
-class StrokeEmulator(DenseOrientEmulator):
-    """DenseOrientEmulator + the editing group of michigan_hip/editing/stroke_orient.h; counts its launches."""
-
-    def __init__(self):
-        super().__init__()
-        self.edit_calls = {"mg_stroke_orient": 0, "mg_stroke_compose": 0, "mg_inpaint_finish": 0}
-
-    def mg_edit_version(self):
-        return 1
-
-    @staticmethod
-    def _fail(fn, msg):
-        raise RuntimeError("%s failed (code 1): %s: %s" % (fn, fn, msg))
-
-    def mg_stroke_orient(self, stroke, bank, rgb_table, rgb_u8, idx, conf, n, h, w, stream=None):
-        self.edit_calls["mg_stroke_orient"] += 1
-        if not (_addr(stroke) and _addr(bank) and _addr(rgb_table) and _addr(rgb_u8)):
-            self._fail("mg_stroke_orient", "null pointer")
-        if n < 1 or h < 1 or w < 1:
-            self._fail("mg_stroke_orient", "bad geometry")
-        res = stroke_contract(_view(stroke, (n, h, w), torch.uint8).numpy(), _view(bank, (32, 17, 17), torch.float32).numpy(),
-                              _view(rgb_table, (32, 3), torch.uint8).numpy())
-        _view(rgb_u8, (n, h, w, 3), torch.uint8)[:] = torch.from_numpy(res["rgb"])
-        if _addr(idx):
-            _view(idx, (n, h, w), torch.uint8)[:] = torch.from_numpy(res["idx"])
-        if _addr(conf):
-            _view(conf, (n, h, w), torch.float32)[:] = torch.from_numpy(res["conf"]).float()
-        return 0
-
-    @staticmethod
-    def _tables(fn, ytab, xtab, ny, nx, sy, sx):
-        if (not _addr(ytab) and ny != sy) or (not _addr(xtab) and nx != sx):
-            StrokeEmulator._fail(fn, "a null table is the identity")
-        return (_view(ytab, (ny,), torch.int32).clamp(0, sy - 1) if _addr(ytab) else None,
-                _view(xtab, (nx,), torch.int32).clamp(0, sx - 1) if _addr(xtab) else None)
-
-    def mg_stroke_compose(self, orient_rgb, noise, hole, stroke, stroke_mask, ytab, xtab, dtype, n, h, w, ho, wo, inp, stream=None):
-        self.edit_calls["mg_stroke_compose"] += 1
-        if not (_addr(orient_rgb) and _addr(noise) and _addr(hole) and _addr(inp)):
-            self._fail("mg_stroke_compose", "null pointer")
-        if bool(_addr(stroke)) != bool(_addr(stroke_mask)):
-            self._fail("mg_stroke_compose", "stroke and stroke_mask are given together or not at all")
-        if dtype not in (0, 1):
-            self._fail("mg_stroke_compose", "bad dtype")
-        if min(n, h, w, ho, wo) < 1:
-            self._fail("mg_stroke_compose", "bad geometry")
-        yt, xt = self._tables("mg_stroke_compose", ytab, xtab, ho, wo, h, w)
-        td = torch.bfloat16 if dtype == 1 else torch.float32
-        v3, v1 = lambda p: _view(p, (n, 3, h, w), torch.float32), lambda p: _view(p, (n, 1, h, w), torch.float32)
-        res = compose_contract(v3(orient_rgb), v3(noise), v1(hole), v3(stroke) if _addr(stroke) else None,
-                               v1(stroke_mask) if _addr(stroke_mask) else None, yt, xt, td)
-        _view(inp, (n, ho, wo, 8), td)[:] = res
-        return 0
-
-    def mg_inpaint_finish(self, net_out, ytab, xtab, hole, orient_rgb, mask, n, h, w, ho, wo, out_rgb, orient2, stream=None):
-        self.edit_calls["mg_inpaint_finish"] += 1
-        if not (_addr(net_out) and _addr(hole) and _addr(orient_rgb) and _addr(mask) and _addr(out_rgb) and _addr(orient2)):
-            self._fail("mg_inpaint_finish", "null pointer")
-        if min(n, h, w, ho, wo) < 1:
-            self._fail("mg_inpaint_finish", "bad geometry")
-        yt, xt = self._tables("mg_inpaint_finish", ytab, xtab, h, w, ho, wo)
-        out, o2 = finish_contract(_view(net_out, (n, 3, ho, wo), torch.float32), yt, xt, _view(hole, (n, 1, h, w), torch.float32),
-                                  _view(orient_rgb, (n, 3, h, w), torch.float32), _view(mask, (n, 1, h, w), torch.float32))
-        _view(out_rgb, (n, 3, h, w), torch.float32)[:] = out
-        _view(orient2, (n, 2, h, w), torch.float32)[:] = o2
-        return 0
-
-
 # ---- the inputs of the fixture -------------------------------------------------------------------------------------------------------
 def polyline_mask(n, h, w, seed):
     """uint8 [n,h,w] in {0, 1}: per sample three to five seeded polylines drawn with PIL.ImageDraw.line, pen widths 1 .. 15 (the UI's
@@ -310,9 +168,3 @@ def kernel_geometry(n, h, w):
     tests/test_gpu_stroke.py asserts TILE_H / TILE_W against the header's MG_STROKE_TILE_*, which the kernel is compiled from."""
     ty, tx = -(-h // TILE_H), -(-w // TILE_W)
     return dict(tile_h=TILE_H, tile_w=TILE_W, tiles_y=ty, tiles_x=tx, blocks=n * ty * tx)
-
-
-def header_defines():
-    """{name: int} of the #defines of include/michigan_hip/editing/stroke_orient.h"""
-    with open(os.path.join(ROOT, "include", "michigan_hip", "editing", "stroke_orient.h")) as fh:
-        return {k: int(v) for k, v in re.findall(r"#define\s+(MG_[A-Z_]+)\s+(\d+)\b", fh.read())}

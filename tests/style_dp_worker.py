@@ -16,9 +16,11 @@ def run(rank, world, port, q):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     torch.set_num_threads(2)
-    import style_loss_emulator as SE
+    import style_loss_fixtures as SE
     from michigan_amd import _cabi, ops
-    _cabi.set_backend(SE.StyleLossEmulator())
+    from oracle import contracts as K
+    from oracle.cabi_emulator import EmulatorBackend
+    _cabi.set_backend(EmulatorBackend())
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     p = SE.make_sets()["i"]
@@ -38,15 +40,15 @@ def run(rank, world, port, q):
     mean = losses.clone()
     dist.all_reduce(mean)
     mean /= world
-    whole_l, whole_g = SE.style_terms(p["x"], p["s"], p["t"], flags=3, weights=SE.WEIGHTS)
+    whole_l, whole_g = K.style_terms(p["x"], p["s"], p["t"], flags=3, weights=SE.WEIGHTS)
     ok["plain_matches"] = bool(((mean - whole_l).abs() <= 1e-6 * whole_l.abs()).all())
     ok["grad_matches"] = float((grad / world - whole_g[rank:rank + 1]).norm() / whole_g[rank:rank + 1].norm()) <= 1e-6
     losses, _ = terms(mine, True)
-    own = SE.style_terms(mine["x"], mine["s"], mine["t"], mine["mask_x"], mine["mask_s"], mine["mask_t"], flags=3)[0]
+    own = K.style_terms(mine["x"], mine["s"], mine["t"], mine["mask_x"], mine["mask_s"], mine["mask_t"], flags=3)[0]
     mean = losses.clone()
     dist.all_reduce(mean)
     mean /= world
-    whole = SE.style_terms(p["x"], p["s"], p["t"], p["mask_x"], p["mask_s"], p["mask_t"], flags=3)[0]
+    whole = K.style_terms(p["x"], p["s"], p["t"], p["mask_x"], p["mask_s"], p["mask_t"], flags=3)[0]
     ok["masked_content_is_per_replica"] = bool(abs(float(losses[1] - own[1])) <= 1e-6 * float(own[1])) and \
         abs(float(mean[1] - whole[1])) > 1e-4 * float(whole[1]) and float(p["mask_t"][0].sum()) != float(p["mask_t"][1].sum())
     q.put((rank, ok))

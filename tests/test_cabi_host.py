@@ -1,4 +1,5 @@
-"""CPU: the C-ABI shared library builds for gfx950, loads, and exports exactly what include/*.h declares."""
+"""CPU: the C-ABI shared library builds for gfx950, loads, and exports exactly what the headers under include/ declare; the ledger
+of the one symbol table (michigan_amd/_cabi.py), the descriptor mirrors and the contract emulator (oracle/cabi_emulator.py)."""
 import ctypes
 import os
 import re
@@ -15,31 +16,65 @@ def lib_path():
 
 
 def _declared_symbols():
+    """every mg_*( declared in a header under include/, sub-folders included, comments stripped"""
     names = set()
-    for fn in os.listdir(os.path.join(ROOT, "include")):
-        if fn.endswith(".h"):
-            src = open(os.path.join(ROOT, "include", fn)).read()
-            src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-            names |= set(re.findall(r"\b(mg_[a-z0-9_]+)\s*\(", src))
+    for folder, _, files in os.walk(os.path.join(ROOT, "include")):
+        for fn in files:
+            if fn.endswith(".h"):
+                src = open(os.path.join(folder, fn)).read()
+                src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+                names |= set(re.findall(r"\b(mg_[a-z0-9_]+)\s*\(", src))
     return names
 
 
 def test_library_exports_every_declared_symbol(lib_path):
+    from michigan_amd import _cabi
     lib = ctypes.CDLL(lib_path)
     declared = _declared_symbols()
     assert len(declared) >= 20
-    for name in declared:
+    for name in declared | set(_cabi.EXPORTED_SYMBOLS):
         assert hasattr(lib, name), f"{name} declared in include/ but not exported"
 
 
 def test_ctypes_mirror_matches_header(lib_path):
+    """One table: what the headers under include/ declare is what michigan_amd/_cabi.py binds, each name once."""
     from michigan_amd import _cabi
-    assert set(_cabi.EXPORTED_SYMBOLS) == _declared_symbols()
+    assert set(_cabi.EXPORTED_SYMBOLS) == _declared_symbols() == set(_cabi._PROTOS)
+    assert len(_cabi.EXPORTED_SYMBOLS) == len(set(_cabi.EXPORTED_SYMBOLS))
+    assert _cabi._NO_STATUS <= set(_cabi.EXPORTED_SYMBOLS)
     be = _cabi.HipBackend(lib_path)
     assert be.mg_abi_version() == _cabi.MG_ABI_VERSION
-    assert be.mg_sizeof_desc(0) == ctypes.sizeof(_cabi.ConvDesc)
-    assert be.mg_sizeof_desc(1) == ctypes.sizeof(_cabi.WgradDesc)
+    with open(os.path.join(ROOT, "include", "michigan_hip.h")) as fh:
+        assert re.search(r"#define\s+MG_ABI_VERSION\s+%d\b" % _cabi.MG_ABI_VERSION, fh.read())
     assert be.mg_stats_workspace(1, 8 * 512 * 512, 128) > 0
+    with pytest.raises(AttributeError):
+        be.mg_not_an_entry_point
+
+
+def test_descriptor_mirrors_match_the_library(lib_path):
+    from michigan_amd import _cabi
+    be = _cabi.HipBackend(lib_path)
+    mirrors = (_cabi.ConvDesc, _cabi.WgradDesc, _cabi.GradSlot, _cabi.PackJob, _cabi.SnLayer, _cabi.NormApply2Desc, _cabi.PyramidDesc,
+               _cabi.FeatMomentDesc)
+    assert _cabi.DESC_MIRRORS == mirrors
+    assert [be.mg_sizeof_desc(which) for which in range(8)] == [ctypes.sizeof(m) for m in mirrors]
+    assert be.mg_sizeof_desc(8) == -1
+    # mg_feat_moment_desc by hand: 6 pointers, 4 int64, 4 int32, 3 pointers, no padding
+    assert ctypes.sizeof(_cabi.FeatMomentDesc) == 6 * 8 + 4 * 8 + 4 * 4 + 3 * 8
+    # by reference: exactly the entry points whose first parameter is a descriptor
+    assert _cabi._BY_REF == {"mg_conv_taps", "mg_conv_wgrad", "mg_wgrad_det_workspace", "mg_norm_bwd_apply2", "mg_nearest_pyramid",
+                             "mg_feat_moment_loss_fwd", "mg_feat_moment_loss_bwd"}
+
+
+def test_emulator_mirrors_the_table():
+    """The contract emulator implements the table, no more and no less, but for the collectives and the probes."""
+    from michigan_amd import _cabi
+    from oracle.cabi_emulator import EmulatorBackend
+    emulated = {name for name in dir(EmulatorBackend) if name.startswith("mg_")}
+    absent = {fn for fn in _cabi.EXPORTED_SYMBOLS if fn.startswith(("mg_comm_", "mg_allreduce_", "mg_probe_"))}
+    assert len(absent) == 8
+    assert emulated == set(_cabi.EXPORTED_SYMBOLS) - absent, sorted(emulated ^ (set(_cabi.EXPORTED_SYMBOLS) - absent))
+    assert all(callable(getattr(EmulatorBackend, name)) for name in emulated)
 
 
 def test_argument_validation_without_gpu(lib_path):

@@ -1,5 +1,5 @@
 """CPU: the fused Lab colour / RGB / background L1 loss (mg_color_loss_*) through every host layer, on the float64 contract
-emulator of its two entry points (tests/color_loss_emulator.py), against what the REFERENCE's own classes computed
+emulator of its two entry points (oracle/cabi_emulator.py, oracle/contracts.py), against what the REFERENCE's own classes computed
 (tests/golden/color_loss_{i,ii}.npz, trainer_C*.npz from tools/make_color_loss_golden.py).
 
   1  the emulator contract vs the reference's float64 run: pins the contract in include/michigan_hip.h to the reference;
@@ -15,9 +15,12 @@ import tempfile
 import pytest
 import torch
 
-import color_loss_emulator as CE
+import color_loss_fixtures as CE
+import parity_utils as PU
+from oracle import contracts as K
 from oracle import ref_harness as R
 from oracle import trainer_parity as TP
+from oracle.cabi_emulator import EmulatorBackend
 
 needs_reference = pytest.mark.skipif(not R.reference_available(), reason="reference checkout not present")
 # tests/test_dropin.py's emulator leg
@@ -30,7 +33,7 @@ pair = CE.load_pair
 @pytest.fixture
 def color_emulator():
     from michigan_amd import _cabi
-    be = CE.ColorLossEmulator()
+    be = EmulatorBackend()
     prev = _cabi.set_backend(be)
     yield be
     _cabi.set_backend(prev)
@@ -39,7 +42,7 @@ def color_emulator():
 @pytest.mark.parametrize("tag", ["i", "ii"])
 def test_contract_matches_the_reference_in_float64(tag):
     fx = pair(tag)
-    losses, grad, _ = CE.color_terms(fx["fake"], fx["real"], fx["back"].float(), 7, tuple(fx["weights"].tolist()))
+    losses, grad, _ = K.color_terms(fx["fake"], fx["real"], fx["back"].float(), 7, tuple(fx["weights"].tolist()))
     for k in range(3):
         assert abs(float(losses[k]) - float(fx["losses"][k])) <= 1e-9 * abs(float(fx["losses"][k])), (k, losses, fx["losses"])
     # every pixel, the ones near a sign change included: float64 on both sides
@@ -69,7 +72,7 @@ def test_ops_color_losses_on_the_emulator(color_emulator, tag, channels):
     assert float(g[..., 3:].abs().max()) == 0.0 if channels > 3 else True
     want = fx["grad"].permute(0, 2, 3, 1)
     assert float((g[..., :3].double() - want).norm() / want.norm()) <= 2e-7
-    assert color_emulator.color_calls == {"fwd": [7], "bwd": [7]}
+    assert color_emulator.flags("mg_color_loss_fwd") == [7] and color_emulator.flags("mg_color_loss_bwd") == [7]
 
 
 def test_loss_classes_alone_and_balance_lab(color_emulator):
@@ -80,7 +83,7 @@ def test_loss_classes_alone_and_balance_lab(color_emulator):
     fake = fx["fake"].clone().requires_grad_(True)                           # plain contiguous NCHW, as the reference's trainer hands over
     lab = networks.LabColorLoss(default_options(gpu_ids=[]))(fake, fx["real"], sem[:, 1:2])
     bg = networks.RGBBackgroundL1Loss()(fake, sem, fx["real"])
-    assert color_emulator.color_calls["fwd"] == [1, 4]                       # one bit each
+    assert color_emulator.flags("mg_color_loss_fwd") == [1, 4]                       # one bit each
     assert abs(float(lab.detach()) - float(fx["losses"][0])) <= 2e-7 * float(fx["losses"][0])
     assert abs(float(bg.detach()) - float(fx["losses"][2])) <= 2e-7 * float(fx["losses"][2])
     (lab + bg).backward()
@@ -89,7 +92,7 @@ def test_loss_classes_alone_and_balance_lab(color_emulator):
     nhwc = torch.zeros(2, 96, 80, 8, dtype=torch.bfloat16)
     nhwc[..., :3] = fx["fake"].permute(0, 2, 3, 1).to(torch.bfloat16)
     view = nhwc.permute(0, 3, 1, 2)[:, :3]
-    want = CE.color_terms(nhwc[..., :3].permute(0, 3, 1, 2).float(), fx["real"], None, 1)[0][0]
+    want = K.color_terms(nhwc[..., :3].permute(0, 3, 1, 2).float(), fx["real"], None, 1)[0][0]
     got = networks.LabColorLoss(default_options(gpu_ids=[]))(view, fx["real"])
     assert abs(float(got) - float(want)) <= 2e-7 * float(want)
     with pytest.raises(NotImplementedError, match="balance_Lab"):
@@ -133,7 +136,7 @@ def _generator_step(color_emulator, same_ref=True, **over):
         data["label_ref"] = data["label_ref"].clone()
         data["label_ref"][:, :, :32] = 0                                     # a hair mask of another area: sum(tag - ref) != 0 (pix2pix_model.py:286)
         assert float((data["label_ref"] - data["label_tag"]).sum()) != 0
-    color_emulator.color_calls["fwd"].clear()
+    color_emulator.calls.clear()
     losses, fake = model(data, mode="generator")
     return losses, fake, data
 
@@ -142,18 +145,18 @@ def test_model_adds_the_keys_under_the_reference_conditions(color_emulator):
     """pix2pix_model.py:317-336: `curr_step == 1 and ref_is_tag`, one switch per term; off by default."""
     base = {"GAN", "GAN_Feat", "VGG", "ORIENT"}
     losses, _, _ = _generator_step(color_emulator)
-    assert set(losses) == base and color_emulator.color_calls["fwd"] == []             # default_options(): all three off
+    assert set(losses) == base and color_emulator.flags("mg_color_loss_fwd") == []             # default_options(): all three off
     subsets = {1: {"lab"}, 2: {"rgb"}, 4: {"background"}, 3: {"lab", "rgb"}, 5: {"lab", "background"}, 6: {"rgb", "background"},
                7: {"lab", "rgb", "background"}}
     for flags, keys in subsets.items():
         losses, _, _ = _generator_step(color_emulator, no_lab_loss=not flags & 1, no_rgb_loss=not flags & 2, no_background_loss=not flags & 4)
         assert set(losses) == base | keys, (flags, set(losses))
-        assert color_emulator.color_calls["fwd"] == [flags]                            # ONE call per generator step, union of the bits
+        assert color_emulator.flags("mg_color_loss_fwd") == [flags]                            # ONE call per generator step, union of the bits
     on = dict(no_lab_loss=False, no_rgb_loss=False, no_background_loss=False)
     losses, _, _ = _generator_step(color_emulator, same_ref=False, **on)
-    assert not {"lab", "rgb", "background"} & set(losses) and color_emulator.color_calls["fwd"] == []   # ref_is_tag false
+    assert not {"lab", "rgb", "background"} & set(losses) and color_emulator.flags("mg_color_loss_fwd") == []   # ref_is_tag false
     losses, _, _ = _generator_step(color_emulator, curr_step=2, **on)
-    assert not {"lab", "rgb", "background"} & set(losses) and color_emulator.color_calls["fwd"] == []   # unpaired step
+    assert not {"lab", "rgb", "background"} & set(losses) and color_emulator.flags("mg_color_loss_fwd") == []   # unpaired step
     from michigan_amd.model import Pix2PixModel
     with pytest.raises(NotImplementedError, match="balance_Lab"):
         Pix2PixModel(TP.repo_options(dict(TP.CFGS["A"], ngf=8, ndf=8, crop=64), no_lab_loss=False, balance_Lab=True))
@@ -163,7 +166,7 @@ def test_model_losses_are_the_contract_values_times_lambda(color_emulator):
     losses, fake, data = _generator_step(color_emulator, no_lab_loss=False, no_rgb_loss=False, no_background_loss=False,
                                          lambda_lab=0.5, lambda_rgb=2.0, lambda_background=3.0)
     back = (data["label_tag"][:, 0] == 0).float()                            # channel 0 of the one-hot label
-    want = CE.color_terms(fake.detach().float(), data["image_tag"], back, 7)[0]
+    want = K.color_terms(fake.detach().float(), data["image_tag"], back, 7)[0]
     for key, k, lam in (("lab", 0, 0.5), ("rgb", 1, 2.0), ("background", 2, 3.0)):
         assert abs(float(losses[key].detach()) - lam * float(want[k])) <= 1e-6 * lam * float(want[k]), key
 
@@ -188,12 +191,12 @@ def test_reference_trainer_with_published_flags_over_dropin(color_emulator):
             assert isinstance(m.criterionLabL1, hip.LabColorLoss) and isinstance(m.criterionBackground, hip.RGBBackgroundL1Loss)
             TP.load_weights(trainer, cfg)
             rec = CE.drive_with_color_losses(trainer, cfg)
-        assert color_emulator.color_calls["fwd"] == [4, 1] * cfg["iters"]              # the reference calls the two classes separately
+        assert color_emulator.flags("mg_color_loss_fwd") == [4, 1] * cfg["iters"]              # the reference calls the two classes separately
     finally:
         dropin.uninstall()
     import models.networks as N
     assert not issubclass(N.LabColorLoss, hip.LabColorLoss)                            # uninstall() put the reference's back
-    TP.compare(rec, CE.load_trainer_golden(), **TOL)
+    TP.compare(rec, PU.load_trainer_golden("C"), **TOL)
 
 
 def test_repo_trainer_matches_reference_golden_with_color_losses(color_emulator):
@@ -203,7 +206,7 @@ def test_repo_trainer_matches_reference_golden_with_color_losses(color_emulator)
     trainer = Pix2PixTrainer(TP.repo_options(cfg, no_lab_loss=False, no_rgb_loss=False, no_background_loss=False))
     TP.load_weights(trainer, cfg)
     rec = CE.drive_with_color_losses(trainer, cfg)
-    assert color_emulator.color_calls["fwd"] == [7] * cfg["iters"]
-    gold = CE.load_trainer_golden()
+    assert color_emulator.flags("mg_color_loss_fwd") == [7] * cfg["iters"]
+    gold = PU.load_trainer_golden("C")
     assert all(("it%d.loss.%s" % (it, k)) in gold for it in range(cfg["iters"]) for k in CE.COLOR_KEYS)
     TP.compare(rec, gold, **TOL)

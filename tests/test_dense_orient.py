@@ -1,25 +1,21 @@
 """CPU: dense hair-orientation extraction (inputs.dense_orientation, python -m michigan_amd.cal_orientation) against what the
 reference's own cal_orientation module computed (tests/golden/dense_orient_{i,ii}.npz, written by
-tools/make_dense_orient_golden.py), on the float64 contract emulator of mg_orient_smooth (tests/dense_orient_emulator.py); and the
-ledger of the preprocessing group of the C ABI (include/michigan_hip/preprocess/*.h), held to the obligations of the other two
-tables (tests/test_cabi_host.py, tests/test_cabi_extensions.py).
+tools/make_dense_orient_golden.py), on the float64 contract emulator of mg_orient_smooth (oracle/cabi_emulator.py,
+oracle/contracts.py).  The ledger of the C ABI is tests/test_cabi_host.py.
 
-Comparison rule for level maps (dense_orient_emulator.rule2): in-mask pixels, circular distance min(d, 255 - d), pixels whose
+Comparison rule for level maps (dense_orient_fixtures.rule2): in-mask pixels, circular distance min(d, 255 - d), pixels whose
 oracle flow magnitude is below 1e-3 of the set's in-mask maximum excluded (at most 0.5 %); bytes equal on >= 99.5 %, within one level
 on all, the angle within 8 x the reference's own fp32-vs-float64 gap; outside the mask every byte equal."""
-import ctypes
-import glob
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-import dense_orient_emulator as DE
+import dense_orient_fixtures as DE
+import parity_utils as PU
+from oracle.cabi_emulator import EmulatorBackend
 
-ROOT = DE.ROOT
-NO_DEVICE_WRITE = {"mg_prep_version"}
 ULP32 = 2.0 ** -23
 
 
@@ -31,7 +27,7 @@ def fixtures():
 @pytest.fixture
 def emulator():
     from michigan_amd import _cabi
-    em = DE.DenseOrientEmulator()
+    em = EmulatorBackend()
     prev = _cabi.set_backend(em)
     yield em
     _cabi.set_backend(prev)
@@ -100,9 +96,9 @@ def _through_the_op(fx, emulator, as_u8=True, layout="nhwc"):
             image = DE.image_fp32(image)
         if layout == "nchw":
             image = image.permute(0, 3, 1, 2).contiguous()
-        before = dict(emulator.prep_calls)
+        before = {k: emulator.count(k) for k in ("mg_gabor_argmax_fwd", "mg_orient_smooth")}
         u8, angle = inputs.dense_orientation(image, torch.from_numpy(rec["mask"]), return_angle=True)
-        assert {k: emulator.prep_calls[k] - before[k] for k in before} == {"mg_gabor_argmax_fwd": 1, "mg_orient_smooth": 1}
+        assert {k: emulator.count(k) - before[k] for k in before} == {"mg_gabor_argmax_fwd": 1, "mg_orient_smooth": 1}
         assert u8.dtype == torch.uint8 and u8.shape == rec["mask"].shape and angle.dtype == torch.float32
         got[geo] = dict(u8=u8.numpy(), theta=angle.numpy())
     return got
@@ -157,13 +153,13 @@ def test_mask_rule_and_refusals(fixtures, emulator):
         inputs.dense_orientation(fimg, mask[:, :-1])
     with pytest.raises(ValueError):
         inputs.dense_orientation(fimg, mask, sigma=4.5)
-    before = dict(emulator.prep_calls)
+    before = list(emulator.calls)
     conf, idx = torch.zeros(1, 16, 40), torch.zeros(1, 16, 40, dtype=torch.uint8)
     with pytest.raises(ValueError):
         ops.orient_smooth(conf, idx, idx)
     with pytest.raises(ValueError):
         ops.orient_smooth(torch.zeros(1, 20, 40), idx, idx)
-    assert emulator.prep_calls == before                                                       # refused before anything is launched
+    assert emulator.calls == before                                                       # refused before anything is launched
 
 
 def _write_pairs(fx, tmp_path, names):
@@ -195,7 +191,7 @@ def test_command_line_single_file(fixtures, emulator, tmp_path, capsys):
                           "--orientation_root", str(out), "--device", "cpu"])
     assert sorted(os.listdir(out)) == ["67172.png"] and capsys.readouterr().out.strip() == str(out / "67172.png")
     _decoded_passes_rule2(out / "67172.png", fixtures["ii"])
-    assert emulator.prep_calls == {"mg_gabor_argmax_fwd": 1, "mg_orient_smooth": 1}
+    assert emulator.count("mg_gabor_argmax_fwd") == 1 and emulator.count("mg_orient_smooth") == 1
 
 
 def test_command_line_directory_in_batches(fixtures, emulator, tmp_path):
@@ -209,54 +205,15 @@ def test_command_line_directory_in_batches(fixtures, emulator, tmp_path):
     maps = [_decoded_passes_rule2(tmp_path / "out" / ("%s.png" % n), fixtures["ii"]) for n in "abc"]
     assert all(np.array_equal(m, maps[0]) for m in maps)
     assert np.array(Image.open(tmp_path / "out" / "d.png")).shape == (100, 90)
-    assert emulator.prep_calls == {"mg_gabor_argmax_fwd": 3, "mg_orient_smooth": 3}             # (a, b), (c), (d)
+    assert emulator.count("mg_gabor_argmax_fwd") == 3 and emulator.count("mg_orient_smooth") == 3             # (a, b), (c), (d)
     os.remove(tmp_path / "masks" / "b.png")
     with pytest.raises(FileNotFoundError):
         cal_orientation.run(str(tmp_path / "images"), str(tmp_path / "masks"), str(tmp_path / "out2"), device="cpu")
 
 
-# ---- 5. the ledger of the preprocessing group --------------------------------------------------------------------------------------------
-def _declared(pattern):
-    names = set()
-    for path in glob.glob(os.path.join(ROOT, "include", pattern)):
-        with open(path) as fh:
-            text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-        names |= set(re.findall(r"\b(mg_[a-z0-9_]+)\s*\(", text))
-    return names
-
-
-def test_preprocess_mirror_matches_the_preprocess_headers():
-    from michigan_amd import _cabi, build
-    prep = _declared(os.path.join("michigan_hip", "preprocess", "*.h"))
-    assert prep and set(_cabi.PREPROCESS_SYMBOLS) == prep == set(_cabi._PREP_PROTOS)
-    assert len(_cabi.PREPROCESS_SYMBOLS) == len(set(_cabi.PREPROCESS_SYMBOLS))
-    assert not prep & set(_cabi.EXPORTED_SYMBOLS) and not prep & set(_cabi.EXTENSION_SYMBOLS)
-    assert not prep & _declared("*.h") and not prep & _declared(os.path.join("michigan_hip", "*.h"))
-    assert "mg_prep_version" in _cabi._NO_STATUS
-    lib = ctypes.CDLL(build.build(verbose=False))
-    for fn in _cabi.PREPROCESS_SYMBOLS:
-        assert hasattr(lib, fn), "%s is declared but not exported" % fn
-    be = _cabi.HipBackend(build.build(verbose=False))
-    assert be.mg_prep_version() == _cabi.MG_PREP_DENSE_ORIENT == DE.header_defines()["MG_PREP_DENSE_ORIENT"]
-    assert DE.DenseOrientEmulator().mg_prep_version() == _cabi.MG_PREP_DENSE_ORIENT
-    with pytest.raises(AttributeError):
-        be.mg_not_an_entry_point
-
-
-def test_every_device_writing_preprocess_symbol_has_a_guarded_case():
-    from michigan_amd import _cabi
-    import test_gpu_dense_orient as GDO
-    prep = set(_cabi.PREPROCESS_SYMBOLS)
-    assert NO_DEVICE_WRITE <= prep
-    covered = {ep for c in GDO.CASES for ep in c.covers}
-    assert covered <= prep | {"mg_gabor_argmax_fwd"} and not covered & NO_DEVICE_WRITE
-    missing = sorted(prep - NO_DEVICE_WRITE - covered)
-    assert not missing, "preprocessing entry points without a guarded case in tests/test_gpu_dense_orient.py: %s" % missing
-    assert len({c.id for c in GDO.CASES}) == len(GDO.CASES)
-
-
+# ---- 5. the tiling the GPU cases sit on --------------------------------------------------------------------------------------------------------
 def test_the_geometry_mirror_is_the_headers_tile():
-    d = DE.header_defines()
+    d = PU.header_defines("michigan_hip/preprocess/dense_orient.h")
     assert (d["MG_ORIENT_TILE_H"], d["MG_ORIENT_TILE_W"], d["MG_ORIENT_RADIUS"]) == (DE.TILE_H, DE.TILE_W, DE.RADIUS)
     g = DE.kernel_geometry(2, 33, 31)
     assert (g["tiles_y"], g["tiles_x"], g["blocks"]) == (2, 1, 4)

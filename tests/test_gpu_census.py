@@ -36,10 +36,10 @@ ACT = {"none": 0, "relu": 1, "lrelu": 2}
 
 
 def install_emulator():
-    """The contract emulator with the colour / hair-Lab entry points (tests/hair_lab_emulator.py); returns the backend it replaced."""
+    """The contract emulator (oracle/cabi_emulator.py); returns the backend it replaced."""
     from michigan_amd import _cabi
-    from hair_lab_emulator import HairLabEmulator
-    return _cabi.set_backend(HairLabEmulator())
+    from oracle.cabi_emulator import EmulatorBackend
+    return _cabi.set_backend(EmulatorBackend())
 
 
 @pytest.fixture

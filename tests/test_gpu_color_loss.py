@@ -14,15 +14,17 @@ Bounds, and where they come from:
             of 4x that and 8 fp32 ulp = 9.5e-7 -- its cbrtf and division are each allowed a couple of ulp by HIP's device-math
             accuracy table and its sums are ordered differently.
             bf16 image: the fixture image is rounded to bf16 first and the reference is the float64 contract
-            (tests/color_loss_emulator.py, pinned to the reference at 1e-9 by tests/test_color_loss.py) on the rounded image, so the
+            (oracle/contracts.py, pinned to the reference at 1e-9 by tests/test_color_loss.py) on the rounded image, so the
             bound measures the kernel and not the input rounding; dimg is written in bf16: one bf16 ulp, 2^-8 relative L2.
   measured  on MI355X (printed by the tests before they assert): see MEASURED below.
 """
 import pytest
 import torch
 
-import color_loss_emulator as CE
-from color_loss_emulator import load_pair as pair
+import color_loss_fixtures as CE
+import parity_utils as PU
+from color_loss_fixtures import load_pair as pair
+from oracle import contracts as K
 from oracle import trainer_parity as TP
 
 pytestmark = pytest.mark.gpu
@@ -68,7 +70,7 @@ def test_kernels_match_the_reference(hip_backend, tag, dtype):
         if tag == "ii":                                            # keep the exactly-equal patch exactly equal after the rounding
             real = real.clone()
             real[:, :, 40:48, 24:32] = rounded[:, :, 40:48, 24:32]
-        want_l, want_g, (da, db, _) = CE.color_terms(rounded, real, fx["back"].float(), 7, weights)
+        want_l, want_g, (da, db, _) = K.color_terms(rounded, real, fx["back"].float(), 7, weights)
         near = lambda t: (t.abs() > 0) & (t.abs() < EXCLUDE_BELOW)
         ex = near(da) | near(db)
         bound = 2.0 ** -8
@@ -122,4 +124,4 @@ def test_trainer_fp32_with_color_losses_matches_reference_trainer_golden(hip_bac
     TP.load_weights(trainer, cfg)
     rec = CE.drive_with_color_losses(trainer, cfg, device="cuda")
     print("trainer C losses", {k: float(v) for k, v in rec.items() if ".loss." in k})
-    TP.compare(rec, CE.load_trainer_golden(), rtol_loss0=5e-4, rtol_later=TP.RTOL_LATER_HIP, atol_img=1e-3, atol_weight=2 * 4e-4 * 2 + 1e-5)
+    TP.compare(rec, PU.load_trainer_golden("C"), rtol_loss0=5e-4, rtol_later=TP.RTOL_LATER_HIP, atol_img=1e-3, atol_weight=2 * 4e-4 * 2 + 1e-5)

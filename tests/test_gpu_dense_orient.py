@@ -2,11 +2,11 @@
 
 1. mg_orient_smooth alone inside guard bands (tests/guard_alloc.py, the machinery of tests/test_gpu_guard_bands.py): each case runs
    ops.orient_smooth under the guard on the HIP backend and on CPU copies with the float64 contract emulator
-   (tests/dense_orient_emulator.py), with idx and conf from the contract of mg_gabor_argmax_fwd on BOTH sides, so ties cannot
+   (oracle/cabi_emulator.py), with idx and conf from the contract of mg_gabor_argmax_fwd on BOTH sides, so ties cannot
    differ; every guard byte is checked, a second run must be bit-identical, and the call-counting backend asserts one call per run.
    Geometries: 2x17x17 (radius 16 reflects onto the far edge; the batch stride 289 is odd), 2x33x47, 2x70x95, and one below / exactly
-   at / one above the kernel's tile in each axis (dense_orient_emulator.kernel_geometry, held to the header the kernel is compiled
-   from); `angle` null and non-null.  ``CASES`` is the ledger tests/test_dense_orient.py checks against ``_cabi.PREPROCESS_SYMBOLS``.
+   at / one above the kernel's tile in each axis (dense_orient_fixtures.kernel_geometry, held to the header the kernel is compiled
+   from); `angle` null and non-null.  ``CASES`` is part of the ledger tests/test_guard_alloc.py checks against ``_cabi.EXPORTED_SYMBOLS``.
    Bounds: rule 2 of tests/test_dense_orient.py (bytes equal on >= 99.5 % of the compared pixels, within one level on all, the angle
    within 8 x the reference's own fp32-vs-float64 gap of the synthetic fixture, every byte outside the mask equal).
 2. The kernel on the reference's own idx and conf, and inputs.dense_orientation end to end, against both fixtures
@@ -22,8 +22,11 @@ import numpy as np
 import pytest
 import torch
 
-import dense_orient_emulator as DE
+import dense_orient_fixtures as DE
+import parity_utils as PU
 import test_gpu_guard_bands as GB
+from oracle import contracts as K
+from oracle.cabi_emulator import EmulatorBackend
 
 pytestmark = pytest.mark.gpu
 
@@ -58,9 +61,9 @@ def _spec(n, h, w, want_angle):
     from michigan_amd import ops
     image, mask = DE.strand_image(n, h, w, 7000 + 100 * h + w)
     mask[:, -1, -1] = 1                                                    # the last pixel of every plane is in the mask
-    conf, idx = DE.argmax_contract(DE.image_fp32(image), ops.dog_bank())
+    conf, idx = K.argmax_contract(DE.image_fp32(image), ops.dog_bank())
     conf, idx = torch.from_numpy(conf).float(), torch.from_numpy(idx).to(torch.uint8)
-    want = DE.smooth_contract(conf.numpy(), idx.numpy(), mask.numpy(), ops.orient_trig_table().numpy(), ops.gaussian_taps(4.0).numpy())
+    want = K.smooth_contract(conf.numpy(), idx.numpy(), mask.numpy(), ops.orient_trig_table().numpy(), ops.gaussian_taps(4.0).numpy())
     magnitude = np.hypot(want["bx"], want["by"])
     pseudo = dict(geometries={"case": dict(mask=mask.numpy(), magnitude=magnitude, u8=want["u8"], level=want["level"])},
                   magnitude_max=float(magnitude[mask.numpy() != 0].max()), ref32_level_gap=_fixture("i")["ref32_level_gap"])
@@ -84,7 +87,7 @@ for _h, _w in ((17, 17), (DE.TILE_H + 1, DE.TILE_W + 1)):
 
 def test_the_cases_sit_on_the_kernels_edges():
     """The mirror is the tile the kernel is compiled with (the header's defines), and the ids' geometry is what the cases build."""
-    d = DE.header_defines()
+    d = PU.header_defines("michigan_hip/preprocess/dense_orient.h")
     assert (d["MG_ORIENT_TILE_H"], d["MG_ORIENT_TILE_W"], d["MG_ORIENT_RADIUS"]) == (DE.TILE_H, DE.TILE_W, DE.RADIUS)
     tiles = lambda h, w: (DE.kernel_geometry(2, h, w)["tiles_y"], DE.kernel_geometry(2, h, w)["tiles_x"])
     assert [tiles(h, w) for h, w in TILE_CASES] == [(1, 2), (1, 2), (2, 2), (2, 1), (2, 1), (2, 2)]
@@ -97,7 +100,6 @@ def test_the_cases_sit_on_the_kernels_edges():
 @pytest.mark.parametrize("c", CASES, ids=[c.id for c in CASES])
 def test_guarded(monkeypatch, c):
     import guard_alloc as GA
-    monkeypatch.setattr(GB, "_emulator", DE.DenseOrientEmulator)      # the contract side needs the preprocessing group's entry point
     counted = []
     orig = GA.Guard.check
 
@@ -112,7 +114,7 @@ def test_guarded(monkeypatch, c):
 def _on_device(fn):
     """fn() on the HIP backend (or, with MG_TEST_DRYRUN=1, on the emulator: plumbing check without a GPU)"""
     from michigan_amd import _cabi
-    prev = _cabi.set_backend(DE.DenseOrientEmulator() if GB.DRY else None)
+    prev = _cabi.set_backend(EmulatorBackend() if GB.DRY else None)
     try:
         if not GB.DRY:
             assert _cabi.backend().name == "hip"

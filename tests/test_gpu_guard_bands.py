@@ -13,7 +13,8 @@ Each case
 0xFF is NaN in every float format: a read outside a tensor that reaches a result, and an output element a kernel never wrote,
 show as a non-finite value in ``_close``.
 
-``CASES`` is also the ledger tests/test_guard_alloc.py checks against ``_cabi.EXPORTED_SYMBOLS``.
+``CASES`` is also part of the ledger tests/test_guard_alloc.py checks against ``_cabi.EXPORTED_SYMBOLS`` (with the cases of
+tests/test_gpu_style_guard_bands.py, test_gpu_dense_orient.py and test_gpu_stroke.py).
 MG_TEST_DRYRUN=1 runs the emulator on both sides (plumbing check on a machine without a GPU).
 
 What the guards cannot see: the split-K scratch of mg_conv_taps and the slab workspace of the thin weight gradient are allocated
@@ -50,8 +51,8 @@ def case(id_, covers):
 
 
 def _emulator():
-    from hair_lab_emulator import HairLabEmulator          # EmulatorBackend + the colour / hair-Lab loss contracts
-    return HairLabEmulator()
+    from oracle.cabi_emulator import EmulatorBackend
+    return EmulatorBackend()
 
 
 class _Ctx:
@@ -927,14 +928,14 @@ def _color_spec(shape, channels):
     """ops.color_losses in fp32 against the float64 contract with the bounds of tests/test_gpu_color_loss.py: losses 1e-4 relative to
     max(1, |want|); gradient 8 fp32 ulp relative L2 over the pixels that are not within 1e-3 of a sign change of da or db (sign() is
     discontinuous there), at most 5e-3 of the pixels left out."""
-    import color_loss_emulator as CE
+    from oracle import contracts as K
     from michigan_amd import ops
     n, h, w = shape
     fx = _loss_fx(n, h, w, h * w)
     img = _image(fx["fake"], channels)
     sem = torch.stack([fx["m_b"], fx["m_f"]], dim=1)
     weights = (1.0, 10.0, 40.0)
-    _, _, (da, db, _) = CE.color_terms(fx["fake"], fx["tgt"], fx["m_b"], 7, weights)
+    _, _, (da, db, _) = K.color_terms(fx["fake"], fx["tgt"], fx["m_b"], 7, weights)
     near = lambda t: (t.abs() > 0) & (t.abs() < 1e-3)
     ex = near(da) | near(db)
     assert float(ex.double().mean()) <= 5e-3
@@ -960,8 +961,8 @@ def _hair_spec(shape, channels):
     fx = _loss_fx(n, h, w, h * w)
     img = _image(fx["fake"], channels)
     sem_tag, sem_ref = torch.stack([fx["m_b"], fx["m_f"]], dim=1), torch.stack([1 - fx["m_r"], fx["m_r"]], dim=1)
-    import hair_lab_emulator as HE
-    _, _, (da, db) = HE.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], fx["tgt"], fx["m_b"], 3, (0.5, 40.0))
+    from oracle import contracts as K
+    _, _, (da, db) = K.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], fx["tgt"], fx["m_b"], 3, (0.5, 40.0))
     assert float(torch.cat([da, db]).abs().min()) >= 1.0, "a mean difference too close to the discontinuity of sign(): pick another seed"
 
     def fn(ctx, img, ref, tgt, sem_tag, sem_ref):

@@ -1,11 +1,11 @@
-"""-m gpu: the stroke route on the kernels of the editing group (mg_stroke.hip).
+"""-m gpu: the stroke route on the kernels of mg_stroke.hip.
 
 1. Each entry point alone inside guard bands (tests/guard_alloc.py, the machinery of tests/test_gpu_guard_bands.py): a case runs the
-   op under the guard on the HIP backend and on CPU copies with the contract emulator (tests/stroke_emulator.py); every guard byte is
-   checked, a second run must be bit-identical, and the call-counting backend asserts one call per run.  ``CASES`` is the ledger
-   tests/test_stroke.py checks against ``_cabi.EDITING_SYMBOLS``.
+   op under the guard on the HIP backend and on CPU copies with the contract emulator (oracle/cabi_emulator.py); every guard byte is
+   checked, a second run must be bit-identical, and the call-counting backend asserts one call per run.  ``CASES`` is part of the
+   ledger tests/test_guard_alloc.py checks against ``_cabi.EXPORTED_SYMBOLS``.
    mg_stroke_orient: 2x1x1, 2x5x40 (smaller than the filter radius), 2x17x17, 2x33x47, one below / exactly at / one above the kernel's
-   tile in each axis (stroke_emulator.kernel_geometry, held to the header the kernel is compiled from), an all-zero mask (zeros
+   tile in each axis (stroke_fixtures.kernel_geometry, held to the header the kernel is compiled from), an all-zero mask (zeros
    everywhere), a single stroke pixel in the last position, and a seeded bank without point symmetry (a correlation, not a
    convolution); idx / conf null and non-null.  Bound: the rule of tests/test_stroke.py against the float64 contract on the case's
    mask, tau from tests/golden/stroke_i.npz (4 x the reference's own fp32-against-float64 figures).
@@ -22,8 +22,11 @@ import numpy as np
 import pytest
 import torch
 
-import stroke_emulator as SE
+import parity_utils as PU
+import stroke_fixtures as SE
 import test_gpu_guard_bands as GB
+from oracle import contracts as K
+from oracle.cabi_emulator import EmulatorBackend
 
 pytestmark = pytest.mark.gpu
 
@@ -70,7 +73,7 @@ def _orient_spec(n, h, w, extras, kind="lines", asymmetric=False):
 
     def check(name, a, r):
         assert torch.isfinite(a).all(), name + ": non-finite"
-        want = SE.stroke_contract(mask, bank, _fixture()["rgb_table"])
+        want = K.stroke_contract(mask, bank, _fixture()["rgb_table"])
         rgb = a[:, :3].permute(0, 2, 3, 1).numpy().astype(np.uint8)
         assert np.array_equal(r[:, :3].permute(0, 2, 3, 1).numpy().astype(np.uint8), want["rgb"]), name + ": the two contract runs differ"
         s = mask != 0
@@ -139,8 +142,8 @@ for _geom in ((2, 32, 32, 256), (2, 33, 47, None)):
 
 def test_the_cases_sit_on_the_kernels_edges():
     """The mirror is the tile the kernel is compiled with (the header's defines), and the ids' geometry is what the cases build."""
-    d = SE.header_defines()
-    assert (d["MG_STROKE_TILE_H"], d["MG_STROKE_TILE_W"], d["MG_STROKE_RADIUS"]) == (SE.TILE_H, SE.TILE_W, SE.RADIUS)
+    d = PU.header_defines("michigan_hip/editing/stroke_orient.h")
+    assert (d["MG_STROKE_TILE_H"], d["MG_STROKE_TILE_W"], d["MG_STROKE_RADIUS"]) == (SE.TILE_H, SE.TILE_W, K.STROKE_RADIUS)
     tiles = lambda h, w: (SE.kernel_geometry(2, h, w)["tiles_y"], SE.kernel_geometry(2, h, w)["tiles_x"])
     assert [tiles(h, w) for h, w in TILE_CASES] == [(1, 2), (1, 2), (2, 2), (2, 1), (2, 1), (2, 2)]
     assert tiles(1, 1) == (1, 1) and tiles(5, 40) == (1, 3) and tiles(33, 47) == (3, 3)
@@ -152,7 +155,6 @@ def test_the_cases_sit_on_the_kernels_edges():
 @pytest.mark.parametrize("c", CASES, ids=[c.id for c in CASES])
 def test_guarded(monkeypatch, c):
     import guard_alloc as GA
-    monkeypatch.setattr(GB, "_emulator", SE.StrokeEmulator)          # the contract side needs the editing group's entry points
     counted = []
     orig = GA.Guard.check
 
@@ -167,7 +169,7 @@ def test_guarded(monkeypatch, c):
 def _on_device(fn):
     """fn(device) on the HIP backend (or, with MG_TEST_DRYRUN=1, on the emulator: plumbing check without a GPU)"""
     from michigan_amd import _cabi
-    prev = _cabi.set_backend(SE.StrokeEmulator() if GB.DRY else None)
+    prev = _cabi.set_backend(EmulatorBackend() if GB.DRY else None)
     try:
         if not GB.DRY:
             assert _cabi.backend().name == "hip"
@@ -197,7 +199,7 @@ def test_stroke_to_orient_end_to_end():
 
 def _glue_fixture():
     import os
-    z = np.load(os.path.join(SE.GOLDEN, "stroke_glue.npz"))
+    z = np.load(os.path.join(PU.GOLDEN, "stroke_glue.npz"))
     return {k: z[k] for k in z.files}
 
 

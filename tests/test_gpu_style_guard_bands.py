@@ -1,11 +1,11 @@
-"""-m gpu: the device-writing entry points of the extension group michigan_hip/feature_losses.h inside guard bands
+"""-m gpu: the device-writing entry points of michigan_hip/feature_losses.h inside guard bands
 (tests/guard_alloc.py), with the machinery of tests/test_gpu_guard_bands.py: each case runs ops.feat_moment_loss forward and backward
 under the guard on the HIP backend, runs the same function on CPU copies with the float64 contract emulator
-(tests/style_loss_emulator.py), compares, checks every guard byte and asserts through the call-counting backend that
+(oracle/cabi_emulator.py), compares, checks every guard byte and asserts through the call-counting backend that
 mg_feat_moment_loss_fwd / _bwd were each called exactly once.  Geometries: one below, exactly at and one above
   * the pixel-chunk multiple (bf16, C = 16: a workgroup row is 128 pixels, the smallest chunk 512 pixels: P = 511, 512, 513), and
   * the channel-tile multiple (fp32: a workgroup owns 256 four-channel vectors: C = 1020, 1024, 1028),
-each unmasked and under masks.  ``CASES`` is the ledger tests/test_cabi_extensions.py checks against ``_cabi.EXTENSION_SYMBOLS``.
+each unmasked and under masks.  ``CASES`` is part of the ledger tests/test_guard_alloc.py checks against ``_cabi.EXPORTED_SYMBOLS``.
 Bounds: those of tests/test_gpu_style_loss.py.
 
 Also here: this package's trainer on the kernels, with the style and content terms on, against the reference trainer's record
@@ -16,7 +16,8 @@ import collections
 import pytest
 import torch
 
-import style_loss_emulator as SE
+import parity_utils as PU
+import style_loss_fixtures as SE
 import test_gpu_guard_bands as GB
 from oracle import trainer_parity as TP
 
@@ -64,7 +65,7 @@ def test_the_cases_sit_on_the_kernels_edges(hip_backend):
     geo = lambda cid: SE.kernel_geometry(*[c for c in CASES if c.id.startswith(cid)][0].build()["geometry"])
     for c in CASES:
         _, n, p, ch = c.build()["geometry"]
-        assert hip_backend.mg_feat_moment_workspace(n, p, ch) == SE.workspace_layout_bytes(n, p, ch), "tests/style_loss_emulator.kernel_geometry is stale"
+        assert hip_backend.mg_feat_moment_workspace(n, p, ch) == SE.workspace_layout_bytes(n, p, ch), "tests/style_loss_fixtures.kernel_geometry is stale"
     below, at, above = (geo("feat_moments-chunk-bf16-2x1x%d" % p) for p in (511, 512, 513))
     assert below["rows"] == 128 and (below["nchunks"], at["nchunks"], above["nchunks"]) == (1, 1, 2) and at["chunk"] == 512
     below, at, above = (geo("feat_moments-ctile-f32-2x3x5x%d" % c) for c in (1020, 1024, 1028))
@@ -74,7 +75,6 @@ def test_the_cases_sit_on_the_kernels_edges(hip_backend):
 @pytest.mark.parametrize("c", CASES, ids=[c.id for c in CASES])
 def test_guarded(monkeypatch, c):
     import guard_alloc as GA
-    monkeypatch.setattr(GB, "_emulator", SE.StyleLossEmulator)      # the contract side needs the extension group's entry points
     counted = []
     orig = GA.Guard.check
 
@@ -94,6 +94,6 @@ def test_trainer_fp32_with_style_and_content_matches_reference_trainer_golden(hi
     SE.load_weights(trainer, cfg)
     rec = SE.drive_style(trainer, cfg, device="cuda")
     print("trainer S losses", {k: float(v) for k, v in rec.items() if ".loss." in k})
-    gold = SE.load_trainer_golden()
+    gold = PU.load_trainer_golden("S")
     assert {k for k in rec if ".loss." in k} == {k for k in gold if ".loss." in k}
     TP.compare(rec, gold, rtol_loss0=5e-4, rtol_later=TP.RTOL_LATER_HIP, atol_img=1e-3, atol_weight=2 * 4e-4 * 2 + 1e-5)

@@ -6,7 +6,7 @@ Bounds, and where they come from (the rule of tests/test_gpu_unpaired.py):
   gradient  relative L2 over ALL elements.
             fp32 features: the larger of 4 x the reference methods' own fp32-vs-float64 error stored in the fixture (set i 6.4e-8
             plain / 7.6e-8 masked, set ii 1.12e-6 plain / 1.16e-7 masked) and 8 fp32 ulp = 9.5e-7.
-            bf16 features: want = the float64 contract (tests/style_loss_emulator.py, pinned to the reference at 1e-9 by
+            bf16 features: want = the float64 contract (oracle/contracts.py, pinned to the reference at 1e-9 by
             tests/test_style_loss.py) on the bf16-rounded features, so the bound measures the kernel and not the input rounding; dx is
             written in bf16: one bf16 ulp, 2^-8.
   measured  on MI355X (printed by the tests before they assert): see MEASURED below.
@@ -14,7 +14,8 @@ Bounds, and where they come from (the rule of tests/test_gpu_unpaired.py):
 import pytest
 import torch
 
-import style_loss_emulator as SE
+import style_loss_fixtures as SE
+from oracle import contracts as K
 
 pytestmark = pytest.mark.gpu
 
@@ -57,7 +58,7 @@ def _want(p, dtype, masked, flags=3, weights=SE.WEIGHTS):
     """The float64 contract on the features as stored in `dtype`."""
     r = lambda k: p[k].to(dtype).float()
     masks = [p[k] for k in MASK_KEYS] if masked else [None] * 3
-    return SE.style_terms(r("x"), r("s"), r("t"), *masks, flags=flags, weights=weights)
+    return K.style_terms(r("x"), r("s"), r("t"), *masks, flags=flags, weights=weights)
 
 
 def _check(name, got, want, dtype, bound):
@@ -140,7 +141,7 @@ GEOMETRIES = [(1, 1, 2, 8), (2, 5, 7, 24), (2, 23, 29, 40)]
 def test_edge_geometries_against_the_contract(hip_backend, shape, dtype, mode):
     n, h, w, c = shape
     geo = SE.kernel_geometry(dtype == torch.bfloat16, n, h * w, c)
-    assert hip_backend.mg_feat_moment_workspace(n, h * w, c) == SE.workspace_layout_bytes(n, h * w, c), "tests/style_loss_emulator.kernel_geometry is stale"
+    assert hip_backend.mg_feat_moment_workspace(n, h * w, c) == SE.workspace_layout_bytes(n, h * w, c), "tests/style_loss_fixtures.kernel_geometry is stale"
     if shape == GEOMETRIES[2]:
         assert geo["nchunks"] >= 3 and (h * w) % geo["chunk"] != 0 and (c // 8) % 2 == 1, geo
     g = torch.Generator().manual_seed(h * w + c)

@@ -8,7 +8,7 @@ Bounds, and where they come from (the rule of tests/test_gpu_color_loss.py, whos
             float64 and on the bf16-rounded image, so sign() is nowhere near its discontinuity.
             fp32 image: the larger of 4 x the reference classes' own fp32-vs-float64 error stored in the fixture (1.24e-7 (i),
             8.7e-8 (ii)) and 8 fp32 ulp = 9.5e-7.
-            bf16 image: want = the float64 contract (tests/hair_lab_emulator.py, pinned to the reference at 1e-9 by
+            bf16 image: want = the float64 contract (oracle/contracts.py, pinned to the reference at 1e-9 by
             tests/test_unpaired.py) on the bf16-rounded image, so the bound measures the kernel and not the input rounding; dimg is
             written in bf16: one bf16 ulp, 2^-8.  The signs of da, db on the rounded image are asserted equal to the fixture's first.
   measured  on MI355X (printed by the tests before they assert): see MEASURED below.
@@ -16,8 +16,10 @@ Bounds, and where they come from (the rule of tests/test_gpu_color_loss.py, whos
 import pytest
 import torch
 
-import hair_lab_emulator as HE
-from hair_lab_emulator import load_pair as pair
+import hair_lab_fixtures as HE
+import parity_utils as PU
+from hair_lab_fixtures import load_pair as pair
+from oracle import contracts as K
 from oracle import trainer_parity as TP
 
 pytestmark = pytest.mark.gpu
@@ -58,7 +60,7 @@ def test_kernels_match_the_reference(hip_backend, tag, dtype):
         bound = max(4 * float(fx["ref32_grad_rel_l2"]), 8 * 2.0 ** -23)
     else:
         rounded = fx["fake"].to(torch.bfloat16).float()
-        want_l, want_g, (da, db) = HE.hair_terms(rounded, fx["ref"], fx["m_f"], fx["m_r"], fx["tgt"], fx["m_b"], 3, weights)
+        want_l, want_g, (da, db) = K.hair_terms(rounded, fx["ref"], fx["m_f"], fx["m_r"], fx["tgt"], fx["m_b"], 3, weights)
         assert torch.equal(torch.sign(da), torch.sign(fx["da"])) and torch.equal(torch.sign(db), torch.sign(fx["db"]))
         bound = 2.0 ** -8
     got_l, got_g = _run(fx, dtype, 8)
@@ -119,7 +121,7 @@ def test_other_geometries_against_the_contract(hip_backend, shape, channels):
           "tgt": rnd(n, 3, h, w) * 2 - 1, "m_f": (rnd(n, h, w) > 0.6).float(), "m_r": (rnd(n, h, w) > 0.5).float()}
     fx["m_b"] = 1 - fx["m_f"]
     weights = (0.5, 40.0)
-    want_l, want_g, (da, db) = HE.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], fx["tgt"], fx["m_b"], 3, weights)
+    want_l, want_g, (da, db) = K.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], fx["tgt"], fx["m_b"], 3, weights)
     assert float(torch.cat([da, db]).abs().min()) >= 1.0, "a mean difference too close to the discontinuity of sign(): pick another seed"
     got_l, got_g = _run(fx, torch.float32, channels, weights=weights)
     got_g3 = got_g[..., :3].permute(0, 3, 1, 2).double()
@@ -139,7 +141,7 @@ def test_trainer_fp32_unpaired_matches_reference_trainer_golden(hip_backend):
     HE.load_weights(trainer, cfg)
     rec = HE.drive_unpaired(trainer, cfg, device="cuda")
     print("trainer U losses", {k: float(v) for k, v in rec.items() if ".loss." in k})
-    gold = HE.load_trainer_golden()
+    gold = PU.load_trainer_golden("U")
     assert {k for k in rec if ".loss." in k} == {k for k in gold if ".loss." in k}
     TP.compare(rec, gold, rtol_loss0=5e-4, rtol_later=TP.RTOL_LATER_HIP, atol_img=1e-3, atol_weight=2 * 4e-4 * 2 + 1e-5)
 

@@ -4,7 +4,8 @@
   * a stand-in backend that writes one element past / before an output's contract extent is caught and the report names the tensor;
   * a stand-in that reads one element past a guarded input yields a non-finite result;
   * the coverage ledger: every exported entry point is either excluded for one of three stated reasons or has a guarded case in
-    tests/test_gpu_guard_bands.py.
+    one of the four GPU case files (tests/test_gpu_guard_bands.py, test_gpu_style_guard_bands.py, test_gpu_dense_orient.py,
+    test_gpu_stroke.py).
 Everything here is host memory inside buffers the test owns: no GPU, nothing faults."""
 import re
 
@@ -12,19 +13,19 @@ import pytest
 import torch
 
 import guard_alloc as GA
+import test_gpu_dense_orient as GDO
 import test_gpu_guard_bands as GB
+import test_gpu_stroke as GS
+import test_gpu_style_guard_bands as GSB
 
-
-def _emulator():
-    from hair_lab_emulator import HairLabEmulator
-    return HairLabEmulator()
+ALL_CASES = GB.CASES + GSB.CASES + GDO.CASES + GS.CASES          # the guarded cases of the four GPU case files
 
 
 @pytest.fixture
 def full_emulator():
-    """The contract emulator with the colour / hair-Lab loss entry points (conftest's emulator_backend is the plain one)."""
+    """A contract emulator of this test's own as the backend."""
     from michigan_amd import _cabi
-    prev = _cabi.set_backend(_emulator())
+    prev = _cabi.set_backend(GB._emulator())
     yield
     _cabi.set_backend(prev)
 
@@ -175,7 +176,7 @@ NO_DEVICE_WRITE = "writes no device memory: it returns a size, a count, a table 
 NEEDS_SEVERAL_GPUS = "needs more than one GPU or RCCL (tests/test_gpu_multirank.py owns these)"
 PROBE = "a hardware-layout probe of the -m gpu suite, not a product kernel"
 EXCLUDED = {
-    "mg_wgrad_det_workspace": NO_DEVICE_WRITE, "mg_stats_workspace": NO_DEVICE_WRITE,
+    "mg_wgrad_det_workspace": NO_DEVICE_WRITE, "mg_stats_workspace": NO_DEVICE_WRITE, "mg_feat_moment_workspace": NO_DEVICE_WRITE,
     "mg_pack_job_blocks": NO_DEVICE_WRITE, "mg_sn_layer_blocks": NO_DEVICE_WRITE, "mg_grad_slot_blocks": NO_DEVICE_WRITE,
     "mg_bicubic_table": NO_DEVICE_WRITE, "mg_nearest_table": NO_DEVICE_WRITE, "mg_orient_rgb_table": NO_DEVICE_WRITE,
     "mg_bicubic_ksize": NO_DEVICE_WRITE, "mg_noise_field_len": NO_DEVICE_WRITE,
@@ -199,10 +200,10 @@ def test_every_device_writing_entry_point_has_a_guarded_case():
         else:
             assert why == NO_DEVICE_WRITE and (fn.endswith(("_workspace", "_blocks", "_table", "_option", "_supported")) or fn in (
                 "mg_bicubic_ksize", "mg_noise_field_len", "mg_abi_version", "mg_last_error", "mg_sizeof_desc")), fn
-    covered = {ep for c in GB.CASES for ep in c.covers}
+    covered = {ep for c in ALL_CASES for ep in c.covers}
     assert covered <= exported, sorted(covered - exported)
     assert not covered & set(EXCLUDED)
     missing = sorted(exported - set(EXCLUDED) - covered)
-    assert not missing, "entry points without a guarded case in tests/test_gpu_guard_bands.py (add one, at its tile-edge geometries): %s" % missing
-    assert len(exported) - len(EXCLUDED) == len(covered) == 57
-    assert len({c.id for c in GB.CASES}) == len(GB.CASES)
+    assert not missing, "entry points without a guarded case in the four GPU case files (add one, at its tile-edge geometries): %s" % missing
+    assert len(EXCLUDED) == 26 and len(exported) - len(EXCLUDED) == len(covered) == 63
+    assert len({c.id for c in ALL_CASES}) == len(ALL_CASES)

@@ -1,19 +1,17 @@
 """CPU: the stroke route of the interactive demo (inputs.stroke_to_orient / stroke_inputs, ops.stroke_compose / inpaint_finish,
 networks.SInpaintGenerator, Pix2PixModel.inpainting_stroke_orient and mode 'demo_inference') against what the reference's own
 modules computed (tests/golden/stroke_i.npz, stroke_glue.npz, sinpaint_state_dict_contract.json, written by
-tools/make_stroke_golden.py), on the contract emulator of the editing group (tests/stroke_emulator.py); and the ledger of that group
-of the C ABI (include/michigan_hip/editing/*.h), held to the obligations of the other three tables.
+tools/make_stroke_golden.py), on the contract emulator of the three entry points (oracle/cabi_emulator.py, oracle/contracts.py).
+The ledger of the C ABI is tests/test_cabi_host.py.
 
-Comparison rule for the stroke picture (stroke_emulator.rule), with tau = 4 x the larger of the reference's own recorded
+Comparison rule for the stroke picture (stroke_fixtures.rule), with tau = 4 x the larger of the reference's own recorded
 fp32-against-float64 figures: at every stroke pixel the float64 response of the returned idx is within tau of the float64 maximum and
 |conf - max| <= tau; idx is the reference's wherever the float64 top-two gap is >= tau (at most 10 % of the stroke pixels are below);
 given idx the RGB bytes are exact; outside the stroke everything is 0; where every response is below -tau, idx and conf are 0."""
 import ctypes
 import functools
-import glob
 import json
 import os
-import re
 import types
 
 import numpy as np
@@ -21,10 +19,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import stroke_emulator as SE
-
-ROOT = SE.ROOT
-NO_DEVICE_WRITE = {"mg_edit_version"}
+import parity_utils as PU
+import stroke_fixtures as SE
+from oracle import contracts as K
+from oracle.cabi_emulator import EmulatorBackend
 
 
 @pytest.fixture(scope="module")
@@ -34,21 +32,21 @@ def fixture():
 
 @pytest.fixture(scope="module")
 def glue():
-    z = np.load(os.path.join(SE.GOLDEN, "stroke_glue.npz"))
+    z = np.load(os.path.join(PU.GOLDEN, "stroke_glue.npz"))
     return {k: z[k] for k in z.files}
 
 
 @pytest.fixture
 def emulator():
     from michigan_amd import _cabi
-    em = SE.StrokeEmulator()
+    em = EmulatorBackend()
     prev = _cabi.set_backend(em)
     yield em
     _cabi.set_backend(prev)
 
 
 def _cfg():
-    with open(os.path.join(SE.GOLDEN, "inpaint_config.json")) as fh:
+    with open(os.path.join(PU.GOLDEN, "inpaint_config.json")) as fh:
         return json.load(fh)
 
 
@@ -117,9 +115,9 @@ def test_stroke_to_orient_on_the_emulator(fixture, emulator):
     got = {}
     for geo, rec in fixture["geometries"].items():
         m = torch.from_numpy(rec["mask"])
-        before = emulator.edit_calls["mg_stroke_orient"]
+        before = emulator.count("mg_stroke_orient")
         rgb = inputs.stroke_to_orient(m)
-        assert emulator.edit_calls["mg_stroke_orient"] == before + 1
+        assert emulator.count("mg_stroke_orient") == before + 1
         assert rgb.dtype == torch.uint8 and tuple(rgb.shape) == m.shape + (3,)
         for other in (m.float(), m.long(), m.bool(), m.unsqueeze(1).double()):
             assert torch.equal(inputs.stroke_to_orient(other), rgb)
@@ -208,13 +206,13 @@ def test_compose_and_finish_are_the_torch_expressions(emulator, geom, strokes):
     w2 = (want_out[:, :-1] - 0.5) * 2
     want_o2 = torch.stack([w2[:, 1], w2[:, 0]], dim=1) * t["mask"]
     assert torch.equal(out, want_out) and torch.equal(o2, want_o2)
-    assert emulator.edit_calls["mg_stroke_compose"] == 2 and emulator.edit_calls["mg_inpaint_finish"] == 1
+    assert emulator.count("mg_stroke_compose") == 2 and emulator.count("mg_inpaint_finish") == 1
 
 
 def test_glue_refusals(emulator):
     from michigan_amd import ops
     t = _glue_tensors(1, 8, 8, 3)
-    before = dict(emulator.edit_calls)
+    before = list(emulator.calls)
     with pytest.raises(ValueError):
         ops.stroke_compose(t["orient_rgb"], t["noise"], t["hole"], t["stroke"], None)
     with pytest.raises(ValueError):
@@ -227,7 +225,7 @@ def test_glue_refusals(emulator):
         ops.inpaint_finish(torch.rand(1, 3, 8, 8).bfloat16(), t["hole"], t["orient_rgb"], t["mask"])
     with pytest.raises(ValueError):
         ops.inpaint_finish(torch.rand(1, 3, 8, 8), t["hole"], t["orient_rgb"], t["mask"][:, :, :4])
-    assert emulator.edit_calls == before                                             # refused before anything is launched
+    assert emulator.calls == before                                             # refused before anything is launched
 
 
 # ---- 6. the network, the model ---------------------------------------------------------------------------------------------------------
@@ -239,7 +237,7 @@ def test_sinpaint_state_dict_contract():
     with torch.device("meta"):
         mine = {k: list(v.shape) for k, v in networks.SInpaintGenerator(opt).state_dict().items()}
         sister = {k: list(v.shape) for k, v in networks.InpaintGenerator(opt).state_dict().items()}
-    with open(os.path.join(SE.GOLDEN, "sinpaint_state_dict_contract.json")) as fh:
+    with open(os.path.join(PU.GOLDEN, "sinpaint_state_dict_contract.json")) as fh:
         contract = json.load(fh)
     assert len(contract) == 124 and list(mine.keys()) == list(contract.keys()) and mine == contract
     assert mine["encoder.1.weight_orig"] == [64, 5, 7, 7] and sister["encoder.1.weight_orig"] == [64, 4, 7, 7]
@@ -284,7 +282,7 @@ def test_inpainting_stroke_orient_on_emulator_matches_golden(emulator, glue):
     e_rgb, e_o2 = np.abs(rgb.numpy() - glue["glue_equal.out_rgb"]).max(), np.abs(o2.numpy() - glue["glue_equal.orient"]).max()
     print("branch equal: rgb %.3g, orient %.3g" % (e_rgb, e_o2))
     assert e_rgb < 2e-4 and e_o2 < 4e-4
-    assert emulator.edit_calls["mg_stroke_compose"] == 1 and emulator.edit_calls["mg_inpaint_finish"] == 1
+    assert emulator.count("mg_stroke_compose") == 1 and emulator.count("mg_inpaint_finish") == 1
 
 
 def test_inpainting_stroke_orient_first_inpainting_on_emulator(emulator, glue):
@@ -299,7 +297,7 @@ def test_inpainting_stroke_orient_first_inpainting_on_emulator(emulator, glue):
     e_rgb, e_o2 = np.abs(rgb.numpy() - glue["glue_less.out_rgb"]).max(), np.abs(o2.numpy() - glue["glue_less.orient"]).max()
     print("branch less, the chain: rgb %.3g, orient %.3g" % (e_rgb, e_o2))
     assert e_rgb < 1e-3 and e_o2 < 2e-3
-    assert emulator.edit_calls["mg_stroke_compose"] == 1 and emulator.edit_calls["mg_inpaint_finish"] == 1
+    assert emulator.count("mg_stroke_compose") == 1 and emulator.count("mg_inpaint_finish") == 1
     own, seen = shim.inpainting_orient, []
 
     def first_pass(*args):
@@ -343,11 +341,11 @@ def test_demo_inference_shapes_and_dtypes(emulator):
     fake, orient_out = model(d, "demo_inference")
     assert tuple(fake.shape) == (n, 3, size, size) and fake.dtype == torch.float32 and torch.isfinite(fake).all()
     assert tuple(orient_out.shape) == (n, size, size, 3) and orient_out.dtype == torch.uint8
-    assert emulator.edit_calls["mg_stroke_compose"] == 1 and emulator.edit_calls["mg_inpaint_finish"] == 1
+    assert emulator.count("mg_stroke_compose") == 1 and emulator.count("mg_inpaint_finish") == 1
     model.opt.inpaint_mode = "ref"                                                   # the demo flips the mode on the live model (demo.py:342-359)
     fake_ref, orient_ref = model(d, "demo_inference")
     assert tuple(orient_ref.shape) == (n, size, size, 3) and orient_ref.dtype == torch.uint8 and tuple(fake_ref.shape) == tuple(fake.shape)
-    assert emulator.edit_calls["mg_stroke_compose"] == 1                             # the existing inpainting_orient, unchanged
+    assert emulator.count("mg_stroke_compose") == 1                             # the existing inpainting_orient, unchanged
     model.opt.inpaint_mode = "stroke"
     with pytest.raises(ValueError, match="mask_stroke"):
         model({k: v for k, v in d.items() if k != "mask_stroke"}, "demo_inference")
@@ -367,53 +365,10 @@ def test_use_stroke_off_builds_no_netsig(emulator):
         model.inpainting_stroke_orient(*[torch.zeros(1, 1, 8, 8)] * 7)
 
 
-# ---- 7. the ledger of the editing group ------------------------------------------------------------------------------------------------
-def _declared(pattern):
-    names = set()
-    for path in glob.glob(os.path.join(ROOT, "include", pattern)):
-        with open(path) as fh:
-            text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-        names |= set(re.findall(r"\b(mg_[a-z0-9_]+)\s*\(", text))
-    return names
-
-
-def test_editing_mirror_matches_the_editing_headers():
-    from michigan_amd import _cabi, build
-    edit = _declared(os.path.join("michigan_hip", "editing", "*.h"))
-    assert edit and set(_cabi.EDITING_SYMBOLS) == edit == set(_cabi._EDIT_PROTOS)
-    assert len(_cabi.EDITING_SYMBOLS) == len(set(_cabi.EDITING_SYMBOLS))
-    for other in (_cabi.EXPORTED_SYMBOLS, _cabi.EXTENSION_SYMBOLS, _cabi.PREPROCESS_SYMBOLS):
-        assert not edit & set(other)
-    for pattern in ("*.h", os.path.join("michigan_hip", "*.h"), os.path.join("michigan_hip", "preprocess", "*.h")):
-        assert not edit & _declared(pattern)
-    assert "mg_edit_version" in _cabi._NO_STATUS
-    assert "mg_stroke.hip" in build.SOURCES
-    lib = ctypes.CDLL(build.build(verbose=False))
-    for fn in _cabi.EDITING_SYMBOLS:
-        assert hasattr(lib, fn), "%s is declared but not exported" % fn
-    be = _cabi.HipBackend(build.build(verbose=False))
-    assert be.mg_edit_version() == _cabi.MG_EDIT_STROKE == SE.header_defines()["MG_EDIT_STROKE"]
-    assert SE.StrokeEmulator().mg_edit_version() == _cabi.MG_EDIT_STROKE
-    assert (_cabi.MG_ABI_VERSION, be.mg_ext_version(), be.mg_prep_version()) == (9, 1, 1)      # the other tables did not move
-    with pytest.raises(AttributeError):
-        be.mg_not_an_entry_point
-
-
-def test_every_device_writing_editing_symbol_has_a_guarded_case():
-    from michigan_amd import _cabi
-    import test_gpu_stroke as GS
-    edit = set(_cabi.EDITING_SYMBOLS)
-    assert NO_DEVICE_WRITE <= edit
-    covered = {ep for c in GS.CASES for ep in c.covers}
-    assert covered <= edit and not covered & NO_DEVICE_WRITE
-    missing = sorted(edit - NO_DEVICE_WRITE - covered)
-    assert not missing, "editing entry points without a guarded case in tests/test_gpu_stroke.py: %s" % missing
-    assert len({c.id for c in GS.CASES}) == len(GS.CASES)
-
-
+# ---- 7. the tiling the GPU cases sit on --------------------------------------------------------------------------------------------------------
 def test_the_geometry_mirror_is_the_headers_tile():
-    d = SE.header_defines()
-    assert (d["MG_STROKE_TILE_H"], d["MG_STROKE_TILE_W"], d["MG_STROKE_RADIUS"], d["MG_STROKE_FILTERS"]) == (SE.TILE_H, SE.TILE_W, SE.RADIUS, 32)
+    d = PU.header_defines("michigan_hip/editing/stroke_orient.h")
+    assert (d["MG_STROKE_TILE_H"], d["MG_STROKE_TILE_W"], d["MG_STROKE_RADIUS"], d["MG_STROKE_FILTERS"]) == (SE.TILE_H, SE.TILE_W, K.STROKE_RADIUS, 32)
     g = SE.kernel_geometry(2, 17, 15)
     assert (g["tiles_y"], g["tiles_x"], g["blocks"]) == (2, 1, 4)
 

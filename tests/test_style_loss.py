@@ -1,5 +1,5 @@
 """CPU: the style / content terms through every host layer, on the float64 contract emulator of mg_feat_moment_loss_fwd /
-mg_feat_moment_loss_bwd (tests/style_loss_emulator.py), against what the REFERENCE's own StyleContentLoss methods and trainer computed
+mg_feat_moment_loss_bwd (oracle/cabi_emulator.py, oracle/contracts.py), against what the REFERENCE's own StyleContentLoss methods and trainer computed
 (tests/golden/style_loss_{i,ii}.npz, trainer_S*.npz from tools/make_style_golden.py).
 
   1  the emulator contract vs the reference's float64 run: pins the contract in include/michigan_hip/feature_losses.h to the reference;
@@ -14,8 +14,11 @@ import socket
 import pytest
 import torch
 
-import style_loss_emulator as SE
+import parity_utils as PU
+import style_loss_fixtures as SE
+from oracle import contracts as K
 from oracle import trainer_parity as TP
+from oracle.cabi_emulator import EmulatorBackend
 
 # tests/test_color_loss.py::TOL
 TOL = dict(rtol_loss0=2e-4, rtol_later=1e-2, atol_img=2e-4, atol_weight=2 * 4e-4 * 2 + 1e-5)
@@ -27,7 +30,7 @@ SETS = SE.make_sets()
 @pytest.fixture
 def style_emulator():
     from michigan_amd import _cabi
-    be = SE.StyleLossEmulator()
+    be = EmulatorBackend()
     prev = _cabi.set_backend(be)
     yield be
     _cabi.set_backend(prev)
@@ -44,24 +47,24 @@ def test_contract_matches_the_reference_in_float64(tag, mode):
     p, fx = SETS[tag], SE.load_set(tag)
     weights = tuple(fx["weights"].tolist())
     assert weights == SE.WEIGHTS
-    losses, grad = SE.style_terms(p["x"], p["s"], p["t"], *_masks(p, mode == "masked"), flags=3, weights=weights)
+    losses, grad = K.style_terms(p["x"], p["s"], p["t"], *_masks(p, mode == "masked"), flags=3, weights=weights)
     want_l, want_g = fx["losses_" + mode], fx["grad_" + mode]
     for k in range(2):
         assert abs(float(losses[k]) - float(want_l[k])) <= 1e-9 * abs(float(want_l[k])), (k, losses, want_l)
     assert float((grad - want_g).norm() / want_g.norm()) <= 1e-9                          # every element
     if tag == "ii" and mode == "masked":
         # "the mask value multiplies": read as a predicate, the fractional rows move each term by far more than the 1e-9 above allows
-        pred = SE.style_terms(p["x"], p["s"], p["t"], *[(m != 0).float() for m in _masks(p, True)], flags=3)[0]
+        pred = K.style_terms(p["x"], p["s"], p["t"], *[(m != 0).float() for m in _masks(p, True)], flags=3)[0]
         for k in range(2):
             assert abs(float(pred[k]) - float(want_l[k])) > 1e-4 * float(want_l[k]), k
         # empty masks: mu = 0, sigma = sqrt(1e-5), nothing is NaN, and the style gradient of the sample with an empty mask_x is exactly 0
         assert float(p["mask_x"][1].sum()) == 0 and float(p["mask_s"][2].sum()) == 0
-        style_only = SE.style_terms(p["x"], p["s"], None, p["mask_x"], p["mask_s"], None, flags=1)[1]
+        style_only = K.style_terms(p["x"], p["s"], None, p["mask_x"], p["mask_s"], None, flags=1)[1]
         assert bool(torch.isfinite(style_only).all()) and float(style_only[1].abs().max()) == 0.0
         assert float((style_only * (p["mask_x"] == 0).unsqueeze(1)).abs().max()) == 0.0
         n, c = p["x"].shape[:2]
-        mu, sg, _, _ = SE.moments(p["x"].double().reshape(n, c, -1), p["mask_x"].double().reshape(n, -1))
-        assert float(mu[1].abs().max()) == 0.0 and float((sg[1] - SE.EPS ** 0.5).abs().max()) == 0.0
+        mu, sg, _, _ = K.moments(p["x"].double().reshape(n, c, -1), p["mask_x"].double().reshape(n, -1))
+        assert float(mu[1].abs().max()) == 0.0 and float((sg[1] - K.FEAT_EPS ** 0.5).abs().max()) == 0.0
 
 
 def test_the_fixture_separates_shifted_from_unshifted_sums():
@@ -97,7 +100,7 @@ def test_ops_feat_moment_loss_on_the_emulator(style_emulator, tag, mode, flags):
     masks = [lab[:, i] for i in range(3)] if masked else [None] * 3
     style, content = ops.feat_moment_loss(x, _nchw_view(p["s"]), _nchw_view(p["t"]), *masks, flags=flags)
     (SE.WEIGHTS[0] * style + SE.WEIGHTS[1] * content).backward()
-    want_g = SE.style_terms(p["x"], p["s"], p["t"], *_masks(p, masked), flags=flags, weights=SE.WEIGHTS)[1]
+    want_g = K.style_terms(p["x"], p["s"], p["t"], *_masks(p, masked), flags=flags, weights=SE.WEIGHTS)[1]
     for k, got in enumerate((style, content)):
         if flags & (1 << k):
             want = float(fx["losses_" + mode][k])
@@ -108,8 +111,8 @@ def test_ops_feat_moment_loss_on_the_emulator(style_emulator, tag, mode, flags):
     assert float((g - want_g).norm() / want_g.norm()) <= GRAD_TOL[tag]
     if flags == 3:
         assert float((g - fx["grad_" + mode]).norm() / fx["grad_" + mode].norm()) <= GRAD_TOL[tag]
-    assert style_emulator.feat_calls == {"fwd": [flags], "bwd": [flags]}       # one forward and one backward call
-    assert style_emulator.hair_calls == {"fwd": [], "bwd": []}
+    assert style_emulator.flags("mg_feat_moment_loss_fwd") == [flags] and style_emulator.flags("mg_feat_moment_loss_bwd") == [flags]       # one forward and one backward call
+    assert style_emulator.flags("mg_hair_lab_fwd") == [] and style_emulator.flags("mg_hair_lab_bwd") == []
 
 
 def test_ops_feat_moment_loss_reads_the_view_in_place_and_checks(style_emulator):
@@ -126,7 +129,7 @@ def test_ops_feat_moment_loss_reads_the_view_in_place_and_checks(style_emulator)
     assert float(plain[0]) == float(style.detach()) and float(plain[1]) == float(content.detach())
     bf = ops.feat_moment_loss(_nchw_view(p["x"], torch.bfloat16), _nchw_view(p["s"], torch.bfloat16), None, flags=1)[0]
     r = lambda k: p[k].to(torch.bfloat16).float()
-    want = SE.style_terms(r("x"), r("s"), None, flags=1)[0][0]
+    want = K.style_terms(r("x"), r("s"), None, flags=1)[0][0]
     assert abs(float(bf) - float(want)) <= 2e-7 * float(want)
     with pytest.raises(ValueError, match="flags"):
         ops.feat_moment_loss(x, s, t, flags=0)
@@ -145,17 +148,16 @@ def test_ops_feat_moment_loss_reads_the_view_in_place_and_checks(style_emulator)
     with pytest.raises(ValueError, match="two pixels"):
         ops.feat_moment_loss(x[:, :, :1, :1], s[:, :, :1, :1], None, flags=1)
     # terms not selected need no operands; nothing flows back when no gradient arrives; one arriving gradient leaves the other NULL
-    calls = style_emulator.feat_calls
-    calls["fwd"].clear()
+    style_emulator.calls.clear()
     style, content = ops.feat_moment_loss(x, None, t, flags=ops.FEAT_CONTENT)
-    assert float(style.detach()) == 0.0 and calls["fwd"] == [2]
+    assert float(style.detach()) == 0.0 and style_emulator.flags("mg_feat_moment_loss_fwd") == [2]
     style, content = ops.feat_moment_loss(x, s, t, *_masks(p, True), flags=3)
     (x.sum() * 0 + 1.0).backward()
-    assert calls["bwd"] == []
+    assert style_emulator.flags("mg_feat_moment_loss_bwd") == []
     x.grad = None
     style.backward()
-    assert calls["bwd"] == [3]
-    want = SE.style_terms(p["x"], p["s"], None, p["mask_x"], p["mask_s"], None, flags=1)[1]
+    assert style_emulator.flags("mg_feat_moment_loss_bwd") == [3]
+    want = K.style_terms(p["x"], p["s"], None, p["mask_x"], p["mask_s"], None, flags=1)[1]
     assert float((x.grad.double() - want).norm() / want.norm()) <= 2e-7
 
 
@@ -201,7 +203,7 @@ def test_loss_class_matches_the_reference_formulation(style_emulator, remove_bac
     fake.requires_grad_(True)
     loss_c, loss_s = crit(fake, style_img, content_img, style_lab, content_lab)
     assert tower.calls == 3
-    assert style_emulator.feat_calls["fwd"] == [1, 1, 1, 1, 3]
+    assert style_emulator.flags("mg_feat_moment_loss_fwd") == [1, 1, 1, 1, 3]
     with torch.no_grad():
         ff, sf, cf = tower(fake), tower(style_img), tower(content_img)
     want_s, swapped = 0.0, 0.0
@@ -209,23 +211,23 @@ def test_loss_class_matches_the_reference_formulation(style_emulator, remove_bac
         size = ff[i].shape[2:]
         ms = F.interpolate(style_lab, size=size, mode="nearest")[:, 0] if remove_background else None
         mc = F.interpolate(content_lab, size=size, mode="nearest")[:, 0] if remove_background else None
-        want_s += float(SE.style_terms(ff[i], sf[i], None, ms, mc, None, flags=1)[0][0])
-        swapped += float(SE.style_terms(ff[i], sf[i], None, mc, ms, None, flags=1)[0][0])
-    want_c = float(SE.style_terms(ff[4], None, cf[4], None, None, mc, flags=2)[0][1])
+        want_s += float(K.style_terms(ff[i], sf[i], None, ms, mc, None, flags=1)[0][0])
+        swapped += float(K.style_terms(ff[i], sf[i], None, mc, ms, None, flags=1)[0][0])
+    want_c = float(K.style_terms(ff[4], None, cf[4], None, None, mc, flags=2)[0][1])
     assert abs(float(loss_s.detach()) - want_s) <= 1e-6 * want_s and abs(float(loss_c.detach()) - want_c) <= 1e-6 * want_c
     if remove_background:
         assert abs(swapped - want_s) > 1e-3 * want_s, "the inputs do not tell the two label assignments apart"
     (loss_c + loss_s).backward()
-    assert style_emulator.feat_calls["bwd"] == [3, 1, 1, 1, 1] and bool(torch.isfinite(fake.grad).all()) and float(fake.grad.abs().max()) > 0
+    assert style_emulator.flags("mg_feat_moment_loss_bwd") == [3, 1, 1, 1, 1] and bool(torch.isfinite(fake.grad).all()) and float(fake.grad.abs().max()) > 0
     # features and masks the caller already has are used as they are; a term that is off runs nothing for it
     tower.calls = 0
-    style_emulator.feat_calls["fwd"].clear()
+    style_emulator.calls.clear()
     loss_c2, loss_s2 = crit(fake, style_img, content_img, style_lab, content_lab, fake_feats=tower(fake), content_feats=cf)
     assert tower.calls == 2 and float(loss_c2.detach()) == float(loss_c.detach()) and float(loss_s2.detach()) == float(loss_s.detach())
     tower.calls = 0
-    style_emulator.feat_calls["fwd"].clear()
+    style_emulator.calls.clear()
     only_c, zero = crit(fake, style_img, content_img, style_lab, content_lab, style=False)
-    assert zero == 0 and tower.calls == 2 and style_emulator.feat_calls["fwd"] == [2] and float(only_c.detach()) == float(loss_c.detach())
+    assert zero == 0 and tower.calls == 2 and style_emulator.flags("mg_feat_moment_loss_fwd") == [2] and float(only_c.detach()) == float(loss_c.detach())
 
 
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------------
@@ -233,7 +235,6 @@ def test_entry_points_validate_their_arguments_without_a_gpu():
     """Like tests/test_cabi_host.py: the real library, arguments refused before anything touches a device."""
     from michigan_amd import _cabi, build
     be = _cabi.HipBackend(build.build(verbose=False))
-    assert be.mg_ext_version() == _cabi.MG_EXT_FEATURE_LOSSES == 1
     assert be.mg_feat_moment_workspace(0, 4, 8) == 0 and be.mg_feat_moment_workspace(1, 4, 6) == 0 and be.mg_feat_moment_workspace(1, 4, 8) > 0
     ok = dict(x=64, s=128, t=192, mask_x=256, mask_s=320, mask_t=384, mask_x_nstride=4, mask_s_nstride=4, mask_t_nstride=4, P=4,
               dtype=_cabi.MG_BF16, N=1, C=8, flags=3, out=448, coef=512, ws=576)
@@ -321,41 +322,40 @@ def test_model_objective_keys_tower_passes_and_call_counts(style_emulator, remov
     model = _model(no_style_loss=False, no_content_loss=False, lambda_style=0.5, lambda_content=3.0, remove_background=remove_background)
     assert model.criterionStyleContent.vgg is model.criterionVGG.vgg, "one tower for the three losses"
     seen = _count_tower(model)
-    calls = style_emulator.feat_calls
     losses, fake = model(_batch(), mode="generator")
     assert set(losses) == {"GAN", "GAN_Feat", "VGG", "ORIENT", "content", "style"}
     assert seen.count(True) == 1, "vgg(fake) runs once for VGG, style and content"
     assert len(seen) == 3, "besides vgg(fake): vgg(image_tag) shared with the VGG loss, vgg(image_ref) for style"
-    assert calls["fwd"] == [1, 1, 1, 1, 3]
+    assert style_emulator.flags("mg_feat_moment_loss_fwd") == [1, 1, 1, 1, 3]
     # the values: the loss class alone on the same inputs
     with torch.no_grad():
         d = model.preprocess_input(_batch())
         c, s = model.criterionStyleContent(fake.detach(), d["image_ref"], d["image_tag"], d["input_ref"][:, 1:2], d["input_tag"][:, 1:2])
     assert abs(float(losses["content"].detach()) - 3.0 * float(c)) <= 1e-6 * 3.0 * float(c)
     assert abs(float(losses["style"].detach()) - 0.5 * float(s)) <= 1e-6 * 0.5 * float(s)
-    calls["fwd"].clear()
+    style_emulator.calls.clear()
     sum(losses.values()).backward()
-    assert sorted(calls["bwd"]) == [1, 1, 1, 1, 3]                             # one backward call per tap
+    assert sorted(style_emulator.flags("mg_feat_moment_loss_bwd")) == [1, 1, 1, 1, 3]                             # one backward call per tap
     assert ("_mg_style_masks" in model.__dict__) == remove_background
     model.drop_input_caches()
     assert "_mg_style_masks" not in model.__dict__
     # the reference is not the target: GAN_Feat and VGG go, content and style stay (pix2pix_model.py:292-319)
     seen.clear()
     losses, _ = model(_batch(unpaired=True), mode="generator")
-    assert set(losses) == {"GAN", "ORIENT", "content", "style"} and calls["fwd"] == [1, 1, 1, 1, 3]
+    assert set(losses) == {"GAN", "ORIENT", "content", "style"} and style_emulator.flags("mg_feat_moment_loss_fwd") == [1, 1, 1, 1, 3]
     assert seen.count(True) == 1 and len(seen) == 3
     # at curr_step 2 neither is computed
     model.opt.curr_step = 2
-    calls["fwd"].clear()
+    style_emulator.calls.clear()
     losses, _ = model(_batch(unpaired=True), mode="generator")
-    assert set(losses) == {"GAN", "ORIENT"} and calls["fwd"] == []
+    assert set(losses) == {"GAN", "ORIENT"} and style_emulator.flags("mg_feat_moment_loss_fwd") == []
     # one of the two: style alone adds vgg(image_ref) only, content alone adds nothing to the tower passes of the VGG loss
     for over, keys, fwd, passes in ((dict(no_style_loss=False), {"style"}, [1] * 5, 3), (dict(no_content_loss=False), {"content"}, [2], 2)):
         m = _model(**over)
         seen = _count_tower(m)
-        calls["fwd"].clear()
+        style_emulator.calls.clear()
         losses, _ = m(_batch(), mode="generator")
-        assert set(losses) == {"GAN", "GAN_Feat", "VGG", "ORIENT"} | keys and calls["fwd"] == fwd and len(seen) == passes and seen.count(True) == 1
+        assert set(losses) == {"GAN", "GAN_Feat", "VGG", "ORIENT"} | keys and style_emulator.flags("mg_feat_moment_loss_fwd") == fwd and len(seen) == passes and seen.count(True) == 1
 
 
 def test_model_with_both_flags_off_calls_nothing(style_emulator):
@@ -364,9 +364,9 @@ def test_model_with_both_flags_off_calls_nothing(style_emulator):
     seen = _count_tower(model)
     losses, _ = model(_batch(), mode="generator")
     assert set(losses) == {"GAN", "GAN_Feat", "VGG", "ORIENT"}
-    assert style_emulator.feat_calls == {"fwd": [], "bwd": []} and len(seen) == 2      # vgg(image_tag), vgg(fake): as before
+    assert style_emulator.flags("mg_feat_moment_loss_fwd") == [] and style_emulator.flags("mg_feat_moment_loss_bwd") == [] and len(seen) == 2      # vgg(image_tag), vgg(fake): as before
     sum(losses.values()).backward()
-    assert style_emulator.feat_calls == {"fwd": [], "bwd": []}
+    assert style_emulator.flags("mg_feat_moment_loss_fwd") == [] and style_emulator.flags("mg_feat_moment_loss_bwd") == []
     assert "_mg_style_masks" not in model.__dict__
 
 
@@ -385,11 +385,11 @@ def test_repo_trainer_matches_reference_golden_with_style_and_content(style_emul
     trainer = Pix2PixTrainer(TP.repo_options(cfg, no_style_loss=False, no_content_loss=False))
     SE.load_weights(trainer, cfg)
     rec = SE.drive_style(trainer, cfg)
-    gold = SE.load_trainer_golden()
+    gold = PU.load_trainer_golden("S")
     for it, keys in SE.STYLE_LOSS_KEYS.items():
         assert {k.split(".")[-1] for k in gold if k.startswith("it%d.loss." % it)} == set(keys)
     assert {k for k in rec if ".loss." in k} == {k for k in gold if ".loss." in k}, "the trainer reports other losses than the reference"
-    assert style_emulator.feat_calls["fwd"] == [1, 1, 1, 1, 3] * cfg["iters"]
+    assert style_emulator.flags("mg_feat_moment_loss_fwd") == [1, 1, 1, 1, 3] * cfg["iters"]
     TP.compare(rec, gold, **TOL)
 
 

@@ -1,5 +1,5 @@
 """CPU: the unpaired training stage (unpairTrain, curr_step = 2) through every host layer, on the float64 contract emulator of
-mg_hair_lab_fwd / mg_hair_lab_bwd (tests/hair_lab_emulator.py), against what the REFERENCE's own classes and trainer computed
+mg_hair_lab_fwd / mg_hair_lab_bwd (oracle/cabi_emulator.py, oracle/contracts.py), against what the REFERENCE's own classes and trainer computed
 (tests/golden/hair_lab_{i,ii}.npz, trainer_U*.npz from tools/make_unpaired_golden.py).
 
   1  the emulator contract vs the reference's float64 run: pins the contract in include/michigan_hip.h to the reference;
@@ -17,9 +17,12 @@ import tempfile
 import pytest
 import torch
 
-import hair_lab_emulator as HE
+import hair_lab_fixtures as HE
+import parity_utils as PU
+from oracle import contracts as K
 from oracle import ref_harness as R
 from oracle import trainer_parity as TP
+from oracle.cabi_emulator import EmulatorBackend
 
 needs_reference = pytest.mark.skipif(not R.reference_available(), reason="reference checkout not present")
 # tests/test_color_loss.py::TOL (tests/test_dropin.py's emulator leg)
@@ -32,7 +35,7 @@ pair = HE.load_pair
 @pytest.fixture
 def hair_emulator():
     from michigan_amd import _cabi
-    be = HE.HairLabEmulator()
+    be = EmulatorBackend()
     prev = _cabi.set_backend(be)
     yield be
     _cabi.set_backend(prev)
@@ -44,18 +47,18 @@ def test_contract_matches_the_reference_in_float64(tag):
     fx = pair(tag)
     made = HE.make_pairs()[tag]
     assert all(torch.equal(made[k], fx[k]) for k in made), "the committed inputs are the seeded ones"
-    losses, grad, (da, db) = HE.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], fx["tgt"], fx["m_b"], 3, tuple(fx["weights"].tolist()))
+    losses, grad, (da, db) = K.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], fx["tgt"], fx["m_b"], 3, tuple(fx["weights"].tolist()))
     for k in range(2):
         assert abs(float(losses[k]) - float(fx["losses"][k])) <= 1e-9 * abs(float(fx["losses"][k])), (k, losses, fx["losses"])
     assert float((grad - fx["grad"]).norm() / fx["grad"].norm()) <= 1e-9                # every element
     assert float((da - fx["da"]).abs().max()) <= 1e-9 * float(fx["da"].abs().max()) and float((db - fx["db"]).abs().max()) <= 1e-9 * float(fx["db"].abs().max())
     assert float(torch.cat([fx["da"], fx["db"]]).abs().min()) >= 1.0                     # what the fixture generator asserted
-    hair_only = HE.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], flags=1)[1]
+    hair_only = K.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], flags=1)[1]
     assert float((hair_only * (fx["m_f"] == 0).unsqueeze(1)).abs().max()) == 0.0
     if tag == "ii":
         # "the mask value multiplies": reading the 0.5 rows as a predicate moves a weighted MEAN only a little (6e-4 here), but that is
         # 10^5 times the 1e-9 the comparison above allows -- the fixture tells the two readings apart
-        pred = HE.hair_terms(fx["fake"], fx["ref"], (fx["m_f"] != 0).float(), fx["m_r"], flags=1)[0][0]
+        pred = K.hair_terms(fx["fake"], fx["ref"], (fx["m_f"] != 0).float(), fx["m_r"], flags=1)[0][0]
         assert abs(float(pred) - float(fx["losses"][0])) > 1e-6 * float(fx["losses"][0])
 
 
@@ -82,7 +85,7 @@ def test_ops_hair_lab_losses_on_the_emulator(hair_emulator, tag, channels, flags
     hair, back = ops.hair_lab_losses(img, fx["ref"], sem_tag[:, 1], sem_ref[:, 1], fx["tgt"], sem_tag[:, 0], flags=flags)
     wh, wb = fx["weights"].tolist()
     (wh * hair + wb * back).backward()
-    want_l, want_g, _ = HE.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], fx["tgt"], fx["m_b"], flags, (wh, wb))
+    want_l, want_g, _ = K.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], fx["tgt"], fx["m_b"], flags, (wh, wb))
     for k, got in enumerate((hair, back)):
         if flags & (1 << k):
             assert abs(float(got.detach()) - float(fx["losses"][k])) <= 2e-7 * float(fx["losses"][k])       # one rounding to the fp32 output
@@ -95,8 +98,8 @@ def test_ops_hair_lab_losses_on_the_emulator(hair_emulator, tag, channels, flags
     assert float((g[..., :3].double() - want).norm() / want.norm()) <= 2e-7
     if flags == 3:
         assert float((g[..., :3].double() - fx["grad"].permute(0, 2, 3, 1)).norm() / fx["grad"].norm()) <= 2e-7
-    assert hair_emulator.hair_calls == {"fwd": [flags], "bwd": [flags]}       # one forward and one backward call
-    assert hair_emulator.color_calls == {"fwd": [], "bwd": []}
+    assert hair_emulator.flags("mg_hair_lab_fwd") == [flags] and hair_emulator.flags("mg_hair_lab_bwd") == [flags]       # one forward and one backward call
+    assert hair_emulator.flags("mg_color_loss_fwd") == [] and hair_emulator.flags("mg_color_loss_bwd") == []
 
 
 def test_ops_hair_lab_losses_checks_and_lazy_backward(hair_emulator):
@@ -116,13 +119,13 @@ def test_ops_hair_lab_losses_checks_and_lazy_backward(hair_emulator):
         ops.hair_lab_losses(img, fx["ref"], sem_tag[:, 1, :-1], sem_ref[:, 1], flags=1)
     # terms not selected need no operands; nothing flows back when no gradient arrives
     hair, back = ops.hair_lab_losses(img, None, None, None, fx["tgt"], sem_tag[:, 0], flags=ops.HAIR_BACKGROUND)
-    assert float(hair.detach()) == 0.0 and hair_emulator.hair_calls["fwd"] == [2]
+    assert float(hair.detach()) == 0.0 and hair_emulator.flags("mg_hair_lab_fwd") == [2]
     hair, back = ops.hair_lab_losses(img, fx["ref"], sem_tag[:, 1], sem_ref[:, 1], fx["tgt"], sem_tag[:, 0], flags=3)
     (img.sum() * 0 + 1.0).backward()
-    assert hair_emulator.hair_calls["bwd"] == []
+    assert hair_emulator.flags("mg_hair_lab_bwd") == []
     hair.backward()                                                          # only one of the two gradients arrives: the other is a NULL pointer
-    assert hair_emulator.hair_calls["bwd"] == [3]
-    want = HE.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], flags=1)[1].permute(0, 2, 3, 1)
+    assert hair_emulator.flags("mg_hair_lab_bwd") == [3]
+    want = K.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], flags=1)[1].permute(0, 2, 3, 1)
     assert float((img.grad.double() - want).norm() / want.norm()) <= 2e-7
 
 
@@ -134,16 +137,16 @@ def test_loss_class_alone_and_balance_lab(hair_emulator):
     fake = fx["fake"].clone().requires_grad_(True)                           # plain contiguous NCHW, as the reference's trainer hands over
     crit = networks.HairAvgLabLoss(default_options(gpu_ids=[]))
     got = crit(fake, fx["ref"], fx["m_f"].unsqueeze(1), fx["m_r"].unsqueeze(1))
-    assert hair_emulator.hair_calls["fwd"] == [1]
+    assert hair_emulator.flags("mg_hair_lab_fwd") == [1]
     assert abs(float(got.detach()) - float(fx["losses"][0])) <= 2e-7 * float(fx["losses"][0])
     got.backward()
-    want = HE.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], flags=1)[1]
+    want = K.hair_terms(fx["fake"], fx["ref"], fx["m_f"], fx["m_r"], flags=1)[1]
     assert fake.grad.shape == fake.shape and float((fake.grad.double() - want).norm() / want.norm()) <= 2e-7
     # the generator's output: an NCHW view of NHWC memory, bf16
     nhwc = torch.zeros(2, HE.H, HE.W, 8, dtype=torch.bfloat16)
     nhwc[..., :3] = fx["fake"].permute(0, 2, 3, 1).to(torch.bfloat16)
     view = nhwc.permute(0, 3, 1, 2)[:, :3]
-    want = HE.hair_terms(nhwc[..., :3].permute(0, 3, 1, 2).float(), fx["ref"], fx["m_f"], fx["m_r"], flags=1)[0][0]
+    want = K.hair_terms(nhwc[..., :3].permute(0, 3, 1, 2).float(), fx["ref"], fx["m_f"], fx["m_r"], flags=1)[0][0]
     got = crit(view, fx["ref"], fx["m_f"].unsqueeze(1), fx["m_r"].unsqueeze(1))
     assert abs(float(got) - float(want)) <= 2e-7 * float(want)
     with pytest.raises(NotImplementedError, match="balance_Lab"):
@@ -155,7 +158,7 @@ def test_entry_points_validate_their_arguments_without_a_gpu():
     """Like tests/test_cabi_host.py: the real library, arguments refused before anything touches a device."""
     from michigan_amd import _cabi, build
     be = _cabi.HipBackend(build.build(verbose=False))
-    assert be.mg_abi_version() == 9 and _cabi.MG_ABI_VERSION == 9
+    assert be.mg_abi_version() == 10 and _cabi.MG_ABI_VERSION == 10
     ok = dict(img=64, ref=64, rs=3 * 64, mf=64, fs=64, mr=64, ms=64, tgt=64, ts=3 * 64, back=64, bs=64, dtype=_cabi.MG_F32, N=1, H=8, W=8, C=8,
               flags=3, out=64, stats=64, ws=64)
 
@@ -226,22 +229,22 @@ def test_model_step_two_objective_and_call_counts(hair_emulator):
     data = _batch()
     losses, fake = model(data, mode="generator")
     assert set(losses) == {"GAN", "ORIENT", "hairAvgLab", "background"}
-    assert hair_emulator.hair_calls["fwd"] == [3] and hair_emulator.color_calls["fwd"] == []
+    assert hair_emulator.flags("mg_hair_lab_fwd") == [3] and hair_emulator.flags("mg_color_loss_fwd") == []
     hair_tag, hair_ref = (data["label_tag"][:, 0] != 0).float(), (data["label_ref"][:, 0] != 0).float()
-    want = HE.hair_terms(fake.detach().float(), data["image_ref"], hair_tag, hair_ref, data["image_tag"], 1 - hair_tag, 3)[0]
+    want = K.hair_terms(fake.detach().float(), data["image_ref"], hair_tag, hair_ref, data["image_tag"], 1 - hair_tag, 3)[0]
     for key, k, lam in (("hairAvgLab", 0, 0.5), ("background", 1, 3.0)):
         assert abs(float(losses[key].detach()) - lam * float(want[k])) <= 1e-6 * lam * float(want[k]), key
     sum(losses.values()).backward()
-    assert hair_emulator.hair_calls == {"fwd": [3], "bwd": [3]}               # 2 + 1 launches for the two image-space terms
+    assert hair_emulator.flags("mg_hair_lab_fwd") == [3] and hair_emulator.flags("mg_hair_lab_bwd") == [3]               # 2 + 1 launches for the two image-space terms
     # the paired half of the same model: no fused call, the usual keys
     model.opt.curr_step = 1
     losses, _ = model(_batch(unpaired=False), mode="generator")
-    assert set(losses) == {"GAN", "GAN_Feat", "VGG", "ORIENT"} and hair_emulator.hair_calls["fwd"] == [3]
+    assert set(losses) == {"GAN", "GAN_Feat", "VGG", "ORIENT"} and hair_emulator.flags("mg_hair_lab_fwd") == [3]
     # curr_step = 2 WITHOUT unpairTrain: GAN + ORIENT only (the reference's condition), no netD2
     plain = _model(curr_step=2)
     assert plain.netD2 is None and not hasattr(plain, "criterionHairAvgLab")
     losses, _ = plain(_batch(), mode="generator")
-    assert set(losses) == {"GAN", "ORIENT"} and hair_emulator.hair_calls["fwd"] == [3]
+    assert set(losses) == {"GAN", "ORIENT"} and hair_emulator.flags("mg_hair_lab_fwd") == [3]
     # background is added at step 2 whatever no_background_loss says, and not twice
     assert TP.repo_options(SMALL).no_background_loss and not TP.repo_options(SMALL).unpairTrain
     from michigan_amd.model import default_options
@@ -369,9 +372,9 @@ def test_repo_trainer_matches_reference_golden_unpaired(hair_emulator):
     trainer = Pix2PixTrainer(TP.repo_options(cfg, unpairTrain=True))
     HE.load_weights(trainer, cfg)
     rec = HE.drive_unpaired(trainer, cfg)
-    assert hair_emulator.hair_calls == {"fwd": [3] * cfg["iters"], "bwd": [3] * cfg["iters"]}     # one fused call per step-2 generator step
-    assert hair_emulator.color_calls["fwd"] == []
-    _check_record(rec, HE.load_trainer_golden(), cfg)
+    assert hair_emulator.flags("mg_hair_lab_fwd") == [3] * cfg["iters"] and hair_emulator.flags("mg_hair_lab_bwd") == [3] * cfg["iters"]     # one fused call per step-2 generator step
+    assert hair_emulator.flags("mg_color_loss_fwd") == []
+    _check_record(rec, PU.load_trainer_golden("U"), cfg)
 
 
 @needs_reference
@@ -401,12 +404,12 @@ def test_reference_trainer_with_unpair_train_over_dropin(hair_emulator):
             HE.load_weights(trainer, cfg)
             rec = HE.drive_unpaired(trainer, cfg)
         # the reference calls its two classes separately
-        assert hair_emulator.hair_calls["fwd"] == [1] * cfg["iters"] and hair_emulator.color_calls["fwd"] == [4] * cfg["iters"]
+        assert hair_emulator.flags("mg_hair_lab_fwd") == [1] * cfg["iters"] and hair_emulator.flags("mg_color_loss_fwd") == [4] * cfg["iters"]
     finally:
         dropin.uninstall()
     import models.networks as N
     assert N.HairAvgLabLoss is ref_cls and RL.HairAvgLabLoss is ref_cls                  # uninstall() put the reference's back
-    _check_record(rec, HE.load_trainer_golden(), cfg)
+    _check_record(rec, PU.load_trainer_golden("U"), cfg)
 
 
 # ---- 10 --------------------------------------------------------------------------------------------------------------------------

@@ -15,12 +15,12 @@ def run(rank, world, port, q):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     torch.set_num_threads(2)
-    import hair_lab_emulator as HE
     from michigan_amd import _cabi, parallel
     from michigan_amd.model import Pix2PixTrainer
     from michigan_amd.synth import synth_loader_batch
     from oracle import trainer_parity as TP
-    be = HE.HairLabEmulator()
+    from oracle.cabi_emulator import EmulatorBackend
+    be = EmulatorBackend()
     _cabi.set_backend(be)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -39,7 +39,7 @@ def run(rank, world, port, q):
     trainer.run_generator_one_step(mine())
     parallel.seed_shared_rng(cfg["seed_py"] + 1)
     trainer.run_discriminator_one_step(mine())
-    ok = {"keys": sorted(trainer.get_latest_losses()), "hair_fwd": list(be.hair_calls["fwd"]), "hair_bwd": list(be.hair_calls["bwd"])}
+    ok = {"keys": sorted(trainer.get_latest_losses()), "hair_fwd": list(be.flags("mg_hair_lab_fwd")), "hair_bwd": list(be.flags("mg_hair_lab_bwd"))}
     ok["netD_untouched"] = all(torch.equal(v, d_before[k]) for k, v in m.netD.state_dict().items())
     ok["netD2_moved"] = any(not torch.equal(v, d2_before[k]) for k, v in m.netD2.named_parameters())
     ok["netG_moved"] = any(not torch.equal(v, g_before[k]) for k, v in m.netG.named_parameters())

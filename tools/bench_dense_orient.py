@@ -1,6 +1,6 @@
 """Dense orientation extraction, measured (GPU box):   python tools/bench_dense_orient.py [--reps 100] [--cpu-reps 2] [--out FILE]
 
-The two launches of inputs.dense_orientation at 8 x 512 x 512 (seeded strand images of tests/dense_orient_emulator.py under an
+The two launches of inputs.dense_orientation at 8 x 512 x 512 (seeded strand images of tests/dense_orient_fixtures.py under an
 elliptical mask, fp32 NHWC on the device):
   * mg_gabor_argmax_fwd under ops.dog_bank and mg_orient_smooth, each alone and the pair back to back, through the operator layer on
     prepared tensors; device events around `--reps` calls after a warm-up, five windows, median and spread.  A time per CALL, launch
@@ -77,7 +77,7 @@ def main():
     args = ap.parse_args()
     assert args.reps >= 50
     assert torch.cuda.is_available(), "this measurement needs the GPU"
-    import dense_orient_emulator as DE
+    import dense_orient_fixtures as DE
     lines = []
 
     def say(s):

@@ -1,7 +1,7 @@
 """The stroke route, measured (GPU box):   python tools/bench_stroke_edit.py [--reps 100] [--cpu-reps 3] [--out FILE]
 
   * inputs.stroke_to_orient (one launch of mg_stroke_orient) at 1 x 512 x 512 -- one pen lift: seeded polylines of
-    tests/stroke_emulator.py, pens 1 .. 15, a few percent of the canvas -- at 8 x 512 x 512 of such canvases, on an empty canvas
+    tests/stroke_fixtures.py, pens 1 .. 15, a few percent of the canvas -- at 8 x 512 x 512 of such canvases, on an empty canvas
     (every tile leaves at once: the launch and the zeros) and on a full one (no tile is skipped: the filter loop's own rate).
     Device events around `--reps` calls after a warm-up, five windows, median and spread.  A time per CALL, launch gap included, not a
     kernel time.  Beside it what the shapes say: the share of 16 x 16 tiles that hold a stroke pixel, and the fp32 FMAs those do.
@@ -79,7 +79,7 @@ def main():
     args = ap.parse_args()
     assert args.reps >= 50
     assert torch.cuda.is_available(), "this measurement needs the GPU"
-    import stroke_emulator as SE
+    import stroke_fixtures as SE
     import test_stroke as TS
     lines = []
 

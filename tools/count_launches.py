@@ -58,7 +58,7 @@ class CountingBackend:
     """Proxy in front of the emulator: every C-ABI call that launches is one HIP launch; aten ops inside it do not count."""
     NO_LAUNCH = ("mg_stats_workspace", "mg_abi_version", "mg_sizeof_desc", "mg_last_error", "mg_grad_slot_blocks", "mg_set_option",
                  "mg_norm_apply2_supported", "mg_nearest_table", "mg_bicubic_table", "mg_bicubic_ksize", "mg_orient_rgb_table",
-                 "mg_noise_field_len", "mg_inputs_set_option", "mg_conv_workspace", "mg_feat_moment_workspace", "mg_ext_version")
+                 "mg_noise_field_len", "mg_inputs_set_option", "mg_feat_moment_workspace")
 
     def __init__(self, inner, census):
         self._inner, self._census = inner, census
@@ -90,13 +90,7 @@ def main():
     census = Census()
     unpaired = "--unpaired" in sys.argv
     style = "--style" in sys.argv and not unpaired
-    if unpaired:
-        from hair_lab_emulator import HairLabEmulator as Emulator
-    elif style:
-        from style_loss_emulator import StyleLossEmulator as Emulator
-    else:
-        Emulator = EmulatorBackend
-    _cabi.set_backend(CountingBackend(Emulator(), census))
+    _cabi.set_backend(CountingBackend(EmulatorBackend(), census))
     torch.manual_seed(0)
     opt = default_options(ngf=8, ndf=8, crop_size=128, gpu_ids=[], compute_dtype="fp32", unpairTrain=unpaired, curr_step=2 if unpaired else 1,
                           no_style_loss=not style, no_content_loss=not style)

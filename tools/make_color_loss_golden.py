@@ -124,7 +124,7 @@ def make_color_loss():
 
 
 def make_trainer():
-    import color_loss_emulator as CE
+    import color_loss_fixtures as CE
     from oracle import ref_harness as R
     from oracle import trainer_parity as TP
     R.setup()

@@ -2,7 +2,7 @@
 
     python tools/make_dense_orient_golden.py        (where the reference checkout is; CPU, seconds)
 
-  tests/golden/dense_orient_i.npz    seeded strand images (tests/dense_orient_emulator.make_sets: N = 2 at 17x17, 33x47 and 70x95 under an
+  tests/golden/dense_orient_i.npz    seeded strand images (tests/dense_orient_fixtures.make_sets: N = 2 at 17x17, 33x47 and 70x95 under an
         elliptical mask; the fixture holds RESULTS only, the images are regenerated from their seed)
   tests/golden/dense_orient_ii.npz   the 128 x 128 crop at row 206, column 72 of the bundled sample 67172 (image and label; the
         pixels are fixture data)
@@ -22,7 +22,7 @@ over the compared pixels), ref32_unequal_bytes, ref32_argmax_flips (shares).
 
 Asserted here, so that no test needs an exclusion list: the acceptance conditions for the reference alone (its fp32 run against its
 float64 run), that the float64 contract of mg_orient_smooth passes rule 2 on both sets, and that every mutant of
-tests/dense_orient_emulator.MUTANTS fails it.
+tests/dense_orient_fixtures.MUTANTS fails it.
 """
 import math
 import os
@@ -86,7 +86,7 @@ def reference_run(CO, image_u8, mask, dtype):
     """One sample: image_u8 [H,W,3], mask [H,W] in {0, 1} -> dict(idx, conf, level, u8, magnitude) with the arithmetic in `dtype`:
     the reference's script lines executed on image_tensor = ToTensor + Normalize(0.5, 0.5) of the image (fp32, then cast)."""
     from scipy.ndimage import gaussian_filter
-    import dense_orient_emulator as DE
+    import dense_orient_fixtures as DE
     cv2 = types.SimpleNamespace(GaussianBlur=lambda a, ksize, sigma: gaussian_filter(a, sigma=sigma, mode="mirror", truncate=4.0))
     assert ksize_free(cv2)
     mask = np.array(mask)
@@ -109,7 +109,7 @@ def ksize_free(cv2):
 
 def crop_of_sample():
     from PIL import Image
-    import dense_orient_emulator as DE
+    import dense_orient_fixtures as DE
     from oracle import ref_harness as R
     r, c, s = DE.CROP
     root = os.path.join(R.REFERENCE_ROOT, "datasets", "FFHQ_demo")
@@ -119,7 +119,7 @@ def crop_of_sample():
 
 
 def make_set(CO, tag, geometries, bank, store_pixels):
-    import dense_orient_emulator as DE
+    import dense_orient_fixtures as DE
     from michigan_amd import ops
     rec = {"bank": bank.numpy(), "bank_maxabs_diff": np.array(float((ops.dog_bank() - bank).abs().max()))}
     runs = {}
@@ -170,7 +170,7 @@ def make_set(CO, tag, geometries, bank, store_pixels):
 
 
 if __name__ == "__main__":
-    import dense_orient_emulator as DE
+    import dense_orient_fixtures as DE
     CO = reference_module()
     bank = reference_bank(CO)
     paths = [make_set(CO, "i", DE.make_sets()["i"], bank, store_pixels=False), make_set(CO, "ii", crop_of_sample(), bank, store_pixels=True)]

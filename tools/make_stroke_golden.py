@@ -2,7 +2,7 @@
 
     python tools/make_stroke_golden.py        (where the reference checkout is; CPU, about a minute)
 
-  tests/golden/stroke_i.npz     seeded polyline masks (tests/stroke_emulator.make_masks: N = 2 at 17x17, 33x47, 70x95 and 128x128, drawn with
+  tests/golden/stroke_i.npz     seeded polyline masks (tests/stroke_fixtures.make_masks: N = 2 at 17x17, 33x47, 70x95 and 128x128, drawn with
         PIL.ImageDraw.line, pen widths 1 .. 15; the fixture holds RESULTS only, the masks are regenerated from their seed)
   tests/golden/stroke_glue.npz  the reference's SInpaintGenerator (eval, synth_state_dict weights, the recipe of inpaint_config.json) on a
         seeded 5-channel 64 x 64 input, and the unbound Pix2PixModel.inpainting_stroke_orient at crop 32 on both of its branches
@@ -21,8 +21,8 @@ indices), and the reference's own fp32-against-float64 figures over the stroke p
 at a pixel where its fp32 arg-max differs) and ref32_resp_err (largest response difference).
 
 Asserted here, so that no test needs an exclusion list: all 32 indices occur inside the strokes, each with one colour; at most 10 % of
-the stroke pixels have a float64 top-two gap below tau; the reference's fp32 run meets the rule of tests/stroke_emulator.rule against
-its float64 run; the float64 contract meets it; every mutant of tests/stroke_emulator.MUTANTS fails it (`convolution` on a seeded bank:
+the stroke pixels have a float64 top-two gap below tau; the reference's fp32 run meets the rule of tests/stroke_fixtures.rule against
+its float64 run; the float64 contract meets it; every mutant of tests/stroke_fixtures.MUTANTS fails it (`convolution` on a seeded bank:
 the reference's bank is point-symmetric bit for bit, which is asserted too, so on it a convolution is the correlation).
 """
 import json
@@ -111,7 +111,7 @@ def summarise(resp):
 
 
 def make_stroke_set(CS, tag="i"):
-    import stroke_emulator as SE
+    import stroke_fixtures as SE
     from michigan_amd import ops
     bank = reference_bank(CS)
     rec = {"bank": bank.numpy()}
@@ -198,7 +198,7 @@ def make_glue():
         first.append(res[0].numpy().copy())
         return res
     shim.inpainting_orient = inpainting_orient
-    import stroke_emulator as SE
+    import stroke_fixtures as SE
     t = SE.glue_inputs(cfg["seed_x"] + 1, crop)
     for branch in ("equal", "less"):
         with torch.no_grad():

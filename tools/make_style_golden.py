@@ -2,7 +2,7 @@
 
     python tools/make_style_golden.py [--no-trainer]        (where the reference checkout is; CPU, ~1 min)
 
-  tests/golden/style_loss_i.npz, style_loss_ii.npz   for the two seeded feature sets of tests/style_loss_emulator.make_sets (the
+  tests/golden/style_loss_i.npz, style_loss_ii.npz   for the two seeded feature sets of tests/style_loss_fixtures.make_sets (the
         fixtures hold RESULTS only, the sets are regenerated from their seed): the reference's StyleContentLoss.calc_style_loss /
         calc_content_loss in FLOAT64 on the fp32 features with remove_background off (`plain`) and on (`masked`), the gradient
         d(w_s style + w_c content) / dx, and the error of the same methods run in FLOAT32 on the CPU against their float64 run -- the
@@ -57,23 +57,23 @@ def reference_run(p, dtype, masked, weights):
 
 def mutant_gradient(p, weights):
     """The unmasked gradient with sigma_x from E[x^2] - mu^2 of UNSHIFTED fp32 sums: what the pivot is there to prevent."""
-    import style_loss_emulator as SE
+    from oracle import contracts as K
     x = p["x"]
     n, c, h, w = x.shape
     P = h * w
     x3 = x.float().reshape(n, c, P)
     s1, s2 = x3.sum(dim=2), (x3 * x3).sum(dim=2)                               # fp32
     mu = (s1 / P).double()
-    sg_x = (((s2 - s1 * s1 / P) / (P - 1)).double().clamp_min(0) + SE.EPS).sqrt()
-    mu_s, sg_s, _, _ = SE.moments(p["s"].double().reshape(n, c, P))
+    sg_x = (((s2 - s1 * s1 / P) / (P - 1)).double().clamp_min(0) + K.FEAT_EPS).sqrt()
+    mu_s, sg_s, _, _ = K.moments(p["s"].double().reshape(n, c, P))
     gm, gs = 2 * (mu - mu_s) / (n * c), 2 * (sg_x - sg_s) / (n * c)
     x64, t64 = x.double().reshape(n, c, P), p["t"].double().reshape(n, c, P)
-    g = SE.gradient(x64, t64, None, None, gm / P, gs / (sg_x * (P - 1)), mu, float(n * P * c), weights[0], weights[1])
+    g = K.gradient(x64, t64, None, None, gm / P, gs / (sg_x * (P - 1)), mu, float(n * P * c), weights[0], weights[1])
     return g.reshape(n, c, h, w)
 
 
 def make_sets():
-    import style_loss_emulator as SE
+    import style_loss_fixtures as SE
     from oracle import ref_harness as R
     R.setup()
     for tag, p in SE.make_sets().items():
@@ -103,7 +103,7 @@ def make_sets():
 
 # ---- the trainer protocol with the two terms on ------------------------------------------------------------------------------------
 def make_trainer():
-    import style_loss_emulator as SP
+    import style_loss_fixtures as SP
     from oracle import ref_harness as R
     from oracle import trainer_parity as TP
     R.setup()

@@ -2,12 +2,12 @@
 
     python tools/make_unpaired_golden.py            (where the reference checkout is; CPU, ~1 min)
 
-  tests/golden/hair_lab_i.npz, hair_lab_ii.npz   two seeded input sets at N=2, 3x96x80 (tests/hair_lab_emulator.make_pairs): the inputs
+  tests/golden/hair_lab_i.npz, hair_lab_ii.npz   two seeded input sets at N=2, 3x96x80 (tests/hair_lab_fixtures.make_pairs): the inputs
         (fp32), the reference's HairAvgLabLoss(fake, ref, m_f, m_r) and RGBBackgroundL1Loss(fake, label, tgt) in FLOAT64 on the
         fp32-rounded inputs, d(w_h hair + w_b background) / d fake, the per-sample da, db, and the error of the same classes run in
         FLOAT32 on the CPU against their float64 run -- the yardstick the fp32 kernel's bound is derived from
         (tests/test_gpu_unpaired.py).
-  tests/golden/trainer_U.npz, trainer_U_weights.npz, trainer_unpaired_config.json   tests/hair_lab_emulator.drive_unpaired's record of
+  tests/golden/trainer_U.npz, trainer_U_weights.npz, trainer_unpaired_config.json   tests/hair_lab_fixtures.drive_unpaired's record of
         the reference's own Pix2PixTrainer on configuration A with the README flags + --unpairTrain: per iteration curr_step = 2 on
         an unpaired batch, then curr_step = 1 on the paired batch (train.py:41-90 in miniature), netD2 seeded as well.
 
@@ -55,7 +55,7 @@ def reference_run(p, dtype, weights):
 
 
 def make_hair_lab():
-    import hair_lab_emulator as HE
+    import hair_lab_fixtures as HE
     from oracle import ref_harness as R
     R.setup()
     for tag, p in HE.make_pairs().items():
@@ -92,7 +92,7 @@ def make_hair_lab():
 
 
 def make_trainer():
-    import hair_lab_emulator as HE
+    import hair_lab_fixtures as HE
     from oracle import ref_harness as R
     from oracle import trainer_parity as TP
     R.setup()
