@@ -16,7 +16,10 @@ same arithmetic runs here as HIP kernels of libmichigan_hip.so on u8 maps that w
     stroke_to_orient   ui_util/cal_orient_stroke.py: the RGB-coded orientation picture of a drawn stroke mask
     stroke_inputs      demo_inference_dataLoad's orient_stroke / mask_stroke / hole tensors (base_dataset.py:214-238)
 
-`DeviceInputPipeline` strings them together into the `data` dict of pix2pix_dataset.py:178-188.  The random
+`DeviceInputPipeline` strings them together into the `data` dict of pix2pix_dataset.py:178-188 (paired, and with image_ref /
+label_ref the unpaired stage's), `inference_batch` into single_inference_dataLoad's (base_dataset.py:49-160) and `demo_batch` into
+demo_inference_dataLoad's (:162-276): every mode Pix2PixModel.forward accepts has its loader here.  The three are compositions of
+the entry points above -- a kernel fused over one batch kind would need an entry point of its own.  The random
 DRAWS stay on the host and follow the reference (random.randint / random.random / random.uniform of a
 `random.Random`); only the Gaussian noise fields come from the device generator.  There is no CPU path:
 every function goes through the C ABI (`_cabi.backend()`), which raises if the library is missing.
@@ -88,10 +91,11 @@ def resize_bicubic_u8(src: torch.Tensor, size, tables=None) -> torch.Tensor:
 
 def crop_u8(src: torch.Tensor, crop: torch.Tensor, size, *, mode: int, unknown_label: int = -1,
             ytab: Optional[torch.Tensor] = None, xtab: Optional[torch.Tensor] = None,
-            mul: Optional[torch.Tensor] = None) -> torch.Tensor:
+            mul: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """src u8 [N,Hs,Ws,C] (or [N,Hs,Ws]); crop int32 [N,3] = (x0, y0, flip) -> fp32 [N,C,H,W].
     mode 0: image (ToTensor + Normalize 0.5/0.5); 1: label-like map (`* 255.0`, 255 -> unknown_label);
-    2: ToTensor only.  `mul` [N,1,H,W] multiplies all channels."""
+    2: ToTensor only.  `mul` [N,1,H,W] multiplies all channels.  `out`: a contiguous fp32 [N,C,H,W] on src's device to
+    write into (the rows of a larger batch whose samples come from sources of different sizes)."""
     src = _u8(src)
     if src.dim() == 3:
         src = src.unsqueeze(-1)
@@ -109,7 +113,10 @@ def crop_u8(src: torch.Tensor, crop: torch.Tensor, size, *, mode: int, unknown_l
     lim_w = ws if xtab is None else xtab.numel()
     if crop_host is not None and (int(crop_host[:, 1].max()) + h > lim_h or int(crop_host[:, 0].max()) + w > lim_w or int(crop_host.min()) < 0):
         raise ValueError("crop window outside the (resized) source")
-    out = torch.empty((n, c, h, w), dtype=torch.float32, device=src.device)
+    if out is None:
+        out = torch.empty((n, c, h, w), dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != (n, c, h, w) or out.dtype != torch.float32 or out.device != src.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous fp32 {(n, c, h, w)} on {src.device}")
     C.backend().mg_input_crop_u8(_p(src), _p(out), _p(crop), _p(ytab), _p(xtab), _p(mul), n, hs, ws, c, h, w,
                                  mode, unknown_label, _stream(src))
     return out
@@ -230,30 +237,80 @@ def stroke_to_orient(mask_stroke: torch.Tensor) -> torch.Tensor:
     return ops.stroke_orient(_stroke_mask_u8(mask_stroke))     # non-zero = stroke; nothing is read back: a pen lift does not wait for the device
 
 
-def stroke_inputs(mask_stroke: torch.Tensor, label_tag: torch.Tensor, mask_hole: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+def stroke_inputs(mask_stroke: torch.Tensor, label_tag: torch.Tensor, mask_hole: Optional[torch.Tensor] = None, *,
+                  crop: Optional[torch.Tensor] = None, ytab: Optional[torch.Tensor] = None,
+                  xtab: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """The stroke entries of demo_inference_dataLoad's batch (base_dataset.py:214-238) at the size of label_tag [N,1,H,W] (the class
     index map as fp32): orient_stroke [N,3,H,W] = ToTensor(stroke picture) * label_tag, mask_stroke [N,1,H,W] = ToTensor(mask) * 255 *
-    label_tag and, when mask_hole is given (the caller dilates the stroke: demo.py:323-324), hole likewise."""
+    label_tag and, when mask_hole is given (the caller dilates the stroke: demo.py:323-324), hole likewise.
+    Without `crop` the stroke mask has label_tag's size (the demo works at the crop size).  With `crop` (host int32 [N,3], the loader's
+    window) the masks are at their stored size and take transform_label's resize (`ytab` / `xtab`: nearest_table of their height /
+    width, None = identity) and crop; the stroke picture is made at the stored size, as the reference makes it (demo.py:325-326)."""
     m = _stroke_mask_u8(mask_stroke)
-    n, h, w = m.shape
+    n = m.shape[0]
     label = label_tag.to(device=m.device, dtype=torch.float32)
-    if tuple(label.shape) != (n, 1, h, w):
-        raise ValueError(f"stroke_inputs: label_tag must be {(n, 1, h, w)}, got {tuple(label_tag.shape)}")
-    zero = torch.zeros((n, 3), dtype=torch.int32)                           # no crop, no flip: the demo works at the crop size
-    out = {"orient_stroke": crop_u8(stroke_to_orient(m), zero, (h, w), mode=2, mul=label),
-           "mask_stroke": crop_u8(m, zero, (h, w), mode=1, mul=label)}
+    if label.dim() != 4 or label.shape[:2] != (n, 1) or (crop is None and tuple(label.shape[2:]) != tuple(m.shape[1:])):
+        raise ValueError(f"stroke_inputs: label_tag must be {(n, 1) + tuple(m.shape[1:])}, got {tuple(label_tag.shape)}")
+    h, w = label.shape[2:]
+    if crop is None:
+        crop = torch.zeros((n, 3), dtype=torch.int32)                       # no crop, no flip: the demo works at the crop size
+    out = {"orient_stroke": crop_u8(stroke_to_orient(m), crop, (h, w), mode=2, ytab=ytab, xtab=xtab, mul=label),
+           "mask_stroke": crop_u8(m, crop, (h, w), mode=1, ytab=ytab, xtab=xtab, mul=label)}
     if mask_hole is not None:
         hm = _stroke_mask_u8(mask_hole.to(m.device))
         if hm.shape != m.shape:
             raise ValueError(f"stroke_inputs: mask_hole {tuple(mask_hole.shape)} does not match the stroke mask's {tuple(m.shape)}")
-        out["hole"] = crop_u8(hm, zero, (h, w), mode=1, mul=label)
+        out["hole"] = crop_u8(hm, crop, (h, w), mode=1, ytab=ytab, xtab=xtab, mul=label)
     return out
 
 
+def _decoded(t, name: str, channels: int, n: Optional[int] = None) -> torch.Tensor:
+    """A decoded file for the loaders below: uint8 [N,H,W] or [H,W] (channels == 1), [N,H,W,3] or [H,W,3] (channels == 3), on any
+    device.  Returns it with the batch dimension; anything else is a ValueError, raised on the host before anything is uploaded."""
+    if not torch.is_tensor(t):
+        raise ValueError(f"{name}: expected a uint8 tensor, got {type(t).__name__}")
+    if t.dtype != torch.uint8:
+        raise ValueError(f"{name}: expected the decoded uint8 bytes, got {t.dtype}")
+    want = 2 if channels == 1 else 3
+    if t.dim() == want:
+        t = t.unsqueeze(0)
+    if t.dim() != want + 1 or (channels == 3 and t.shape[-1] != 3) or min(t.shape) < 1:
+        raise ValueError(f"{name}: expected {'[N,H,W] or [H,W]' if channels == 1 else '[N,H,W,3] or [H,W,3]'}, got {tuple(t.shape)}")
+    if n is not None and t.shape[0] != n:
+        raise ValueError(f"{name}: batch of {t.shape[0]}, the other maps have {n}")
+    return t
+
+
+def _same_size(maps: Dict[str, torch.Tensor]):
+    """maps that one reference function combines pixel by pixel at their stored size"""
+    sizes = {k: tuple(v.shape[1:3]) for k, v in maps.items()}
+    if len(set(sizes.values())) > 1:
+        raise ValueError("these maps must have one size: %s" % sizes)
+
+
+def _pad_zeros(t: torch.Tensor, th: int) -> torch.Tensor:
+    """pad_zeros (base_dataset.py:28-47) on u8 [N,H,W] / [N,H,W,C]: H + th by W + th, the map int(th / 2) from the top left"""
+    o = int(th / 2)
+    out = t.new_zeros((t.shape[0], t.shape[1] + th, t.shape[2] + th) + tuple(t.shape[3:]))
+    out[:, o:o + t.shape[1], o:o + t.shape[2]] = t
+    return out
+
+
+def _loader_device(tensors) -> torch.device:
+    """where inference_batch / demo_batch work: the device of the first map that is on one, else the current device of the backend"""
+    for t in tensors:
+        if torch.is_tensor(t) and t.is_cuda:
+            return t.device
+    return torch.device("cuda", torch.cuda.current_device()) if C.backend().name == "hip" else torch.device("cpu")
+
+
 class DeviceInputPipeline:
-    """Pix2pixDataset.__getitem__ (step 1: reference == target, pix2pix_dataset.py:66-194) for a whole batch on the
-    device.  Inputs are the decoded bytes at their stored size: images u8 [N,Hs,Ws,3] (bicubic-resized to load size here,
-    Pillow-exact), label / orientation maps u8 [N,Hs,Ws] (nearest-resized)."""
+    """Pix2pixDataset.__getitem__ (pix2pix_dataset.py:66-194) for a whole batch on the device.  Inputs are the decoded bytes at
+    their stored size: images u8 [N,Hs,Ws,3] (bicubic-resized to load size here, Pillow-exact), label / orientation maps u8
+    [N,Hs,Ws] (nearest-resized).  Without image_ref / label_ref this is step 1 (the reference is the target); with them it is the
+    unpaired stage's batch (step 2, `index_ref` another sample, :75-100).  WHICH sample is the reference, and whose mask
+    `orient_mask` is (:124-126), stays the dataset's choice: the caller draws the indices and hands over the decoded files.
+    `inference_batch` and `demo_batch` are base_dataset.py's two single-sample loaders on the same launches."""
 
     def __init__(self, opt, device, rng: Optional[_random.Random] = None, generator: Optional[torch.Generator] = None):
         self.opt, self.device = opt, torch.device(device)
@@ -271,6 +328,15 @@ class DeviceInputPipeline:
             self._tabs[src] = nearest_table(src, self.load_size, self.device)
         return self._tabs[src]
 
+    def _tabs_for(self, hs: int, ws: int):
+        """(ytab, xtab) of a map stored at hs x ws.  mg_input_crop_u8 takes both tables or none, so where one axis is at the load
+        size already its identity is written out."""
+        yt, xt = self._tab(hs), self._tab(ws)
+        if (yt is None) != (xt is None):
+            ident = torch.arange(self.load_size, dtype=torch.int32, device=self.device)
+            yt, xt = (ident if yt is None else yt), (ident if xt is None else xt)
+        return yt, xt
+
     def draw_params(self, n: int) -> torch.Tensor:
         """get_params (base_dataset.py:398-416), 'resize_and_crop': the same three draws per sample."""
         rows = []
@@ -281,19 +347,75 @@ class DeviceInputPipeline:
             rows.append([x, y, int(flip and self.flip)])
         return torch.tensor(rows, dtype=torch.int32)
 
-    def __call__(self, image: torch.Tensor, label: torch.Tensor, orient: torch.Tensor,
-                 orient_mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        opt, dev, cs = self.opt, self.device, self.crop_size
-        image, label, orient = (t.to(dev) for t in (image, label, orient))
-        n = image.shape[0]
-        if image.shape[1] != self.load_size or image.shape[2] != self.load_size:       # Resize(osize, BICUBIC), base_dataset.py:421-424
+    def _window(self, n: int) -> torch.Tensor:
+        """the batch's draws, checked on the host, before the upload"""
+        crop_h = self.draw_params(n)
+        if int(crop_h[:, :2].min()) < 0 or int(crop_h[:, :2].max()) + self.crop_size > self.load_size:
+            raise ValueError("crop window outside the load_size x load_size source")
+        return crop_h
+
+    def _resized(self, image: torch.Tensor) -> torch.Tensor:
+        """Resize(osize, BICUBIC), base_dataset.py:421-424"""
+        if image.shape[1] != self.load_size or image.shape[2] != self.load_size:
             key = (image.shape[1], image.shape[2])
             if key not in self._btabs:
-                self._btabs[key] = (bicubic_table(key[1], self.load_size, dev), bicubic_table(key[0], self.load_size, dev))
+                self._btabs[key] = (bicubic_table(key[1], self.load_size, self.device), bicubic_table(key[0], self.load_size, self.device))
             image = resize_bicubic_u8(image, self.load_size, self._btabs[key])
-        crop_h = self.draw_params(n)
-        if int(crop_h[:, :2].min()) < 0 or int(crop_h[:, :2].max()) + cs > self.load_size:      # checked on the host, before the upload
-            raise ValueError("crop window outside the load_size x load_size source")
+        return image
+
+    def _image(self, image: torch.Tensor, crop: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """transform_image: an image stored at any size through the tables of that size"""
+        return crop_u8(self._resized(image.to(self.device)), crop, self.crop_size, mode=0, out=out)
+
+    def _map(self, src: torch.Tensor, crop: torch.Tensor, *, mode: int, unknown_label: int = -1, mul: Optional[torch.Tensor] = None,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """transform_label: a map (or an RGB picture) stored at any size through the tables of that size"""
+        yt, xt = self._tabs_for(src.shape[1], src.shape[2])
+        return crop_u8(src.to(self.device), crop, self.crop_size, mode=mode, unknown_label=unknown_label, ytab=yt, xtab=xt, mul=mul, out=out)
+
+    def _each(self, fn, sources, crop: torch.Tensor, channels: int, **kw) -> torch.Tensor:
+        """a batch whose samples are stored at different sizes: one launch per sample into its rows of the batch"""
+        out = torch.empty((len(sources), channels, self.crop_size, self.crop_size), dtype=torch.float32, device=self.device)
+        for i, s in enumerate(sources):
+            fn(s, crop[i:i + 1], out=out[i:i + 1], **kw)
+        return out
+
+    def _check_options(self, what: str):
+        if getattr(self.opt, "color_jitter", False):
+            raise NotImplementedError(f"{what}: color_jitter (torchvision's ColorJitter on the reference image) is not implemented")
+        mode = getattr(self.opt, "preprocess_mode", "resize_and_crop")
+        if mode != "resize_and_crop":
+            raise NotImplementedError(f"{what}: preprocess_mode {mode!r}; only 'resize_and_crop' is implemented")
+        if self.crop_size > self.load_size:                                     # get_params would draw x = y = 0: no window fits
+            raise ValueError(f"{what}: crop window outside the load size ({self.crop_size} > {self.load_size})")
+
+    def __call__(self, image: torch.Tensor, label: torch.Tensor, orient: torch.Tensor, orient_mask: Optional[torch.Tensor] = None,
+                 image_ref=None, label_ref=None) -> Dict[str, torch.Tensor]:
+        """image_ref / label_ref (both or neither): the decoded files of the reference sample, [N,Hr,Wr,3] / [N,Hr,Wr], or a
+        sequence of N per-sample tensors [Hr,Wr,3] / [Hr,Wr] where their sizes differ within the batch.  They take the target's
+        window and flip (the reference reuses `params` and `transform_label`) through the tables of their own size."""
+        opt, dev, cs = self.opt, self.device, self.crop_size
+        self._check_options("DeviceInputPipeline")
+        if (image_ref is None) != (label_ref is None):
+            raise ValueError("image_ref and label_ref are given together (the reference sample's two files), or neither")
+        n = image.shape[0]
+        for name, t in (("label", label), ("orient", orient), ("orient_mask", orient_mask)):       # combined pixel by pixel at the stored size
+            if t is not None and (t.shape[0] != n or tuple(t.shape[1:3]) != tuple(label.shape[1:3])):
+                raise ValueError(f"{name} {tuple(t.shape)} does not match the batch: {n} samples, label {tuple(label.shape)}")
+        if image_ref is not None:
+            listed = isinstance(image_ref, (list, tuple))
+            if listed != isinstance(label_ref, (list, tuple)):
+                raise ValueError("image_ref and label_ref are both batches or both sequences of per-sample tensors")
+            if listed:
+                if len(image_ref) != n or len(label_ref) != n:
+                    raise ValueError(f"image_ref / label_ref: {len(image_ref)} / {len(label_ref)} samples, the batch has {n}")
+                image_ref = [_decoded(t, "image_ref[%d]" % i, 3, 1) for i, t in enumerate(image_ref)]
+                label_ref = [_decoded(t, "label_ref[%d]" % i, 1, 1) for i, t in enumerate(label_ref)]
+            else:
+                image_ref, label_ref = _decoded(image_ref, "image_ref", 3, n), _decoded(label_ref, "label_ref", 1, n)
+        image, label, orient = (t.to(dev) for t in (image, label, orient))
+        image = self._resized(image)
+        crop_h = self._window(n)
         crop = crop_h.to(dev)
         yt, xt = self._tab(label.shape[1]), self._tab(label.shape[2])
         unknown = int(opt.label_nc)
@@ -312,4 +434,120 @@ class DeviceInputPipeline:
         else:
             data["orient_rgb"], data["hole"] = torch.tensor(0), 0
         data["noise"] = generate_noise(n, cs, dev, self.generator)
+        if image_ref is not None:                                               # pix2pix_dataset.py:80-83,96-100
+            if isinstance(image_ref, list):
+                data["label_ref"] = self._each(self._map, label_ref, crop, 1, mode=1, unknown_label=unknown)
+                data["image_ref"] = self._each(self._image, image_ref, crop, 3)
+            else:
+                data["label_ref"] = self._map(label_ref, crop, mode=1, unknown_label=unknown)
+                data["image_ref"] = self._image(image_ref, crop)
         return data
+
+    def inference_batch(self, *, image_ref, image_tag, label_ref, label_tag, orient_tag, orient_ref, orient_mask,
+                        same_orient: bool) -> Dict[str, torch.Tensor]:
+        """single_inference_dataLoad (base_dataset.py:49-160) from its seven decoded files; the keys it returns, except `path`.
+        same_orient: `opt.inference_orient_name == opt.inference_tag_name`, the hole rule's case (:116)."""
+        opt, dev = self.opt, self.device
+        self._check_options("inference_batch")
+        if getattr(opt, "expand_tag_mask", False):
+            raise NotImplementedError("inference_batch: expand_tag_mask (a 25 x 25 cv2.dilate of the target mask) is not implemented")
+        label_tag = _decoded(label_tag, "label_tag", 1)
+        n = label_tag.shape[0]
+        label_ref, orient_tag, orient_ref, orient_mask = (_decoded(t, k, 1, n) for k, t in (
+            ("label_ref", label_ref), ("orient_tag", orient_tag), ("orient_ref", orient_ref), ("orient_mask", orient_mask)))
+        image_ref, image_tag = _decoded(image_ref, "image_ref", 3, n), _decoded(image_tag, "image_tag", 3, n)
+        ig = bool(getattr(opt, "use_ig", False))
+        if ig:          # trans_orient_to_rgb (:107) and generate_hole (:117-118) combine them at their stored size
+            _same_size({"label_tag": label_tag, "orient_mask": orient_mask, "orient_ref": orient_ref})
+        if getattr(opt, "add_zeros", False):                                    # :69-76, before anything else
+            th = int(opt.add_th)
+            label_ref, label_tag, orient_mask, orient_tag, orient_ref, image_ref, image_tag = (
+                _pad_zeros(t, th) for t in (label_ref, label_tag, orient_mask, orient_tag, orient_ref, image_ref, image_tag))
+        crop = self._window(n).to(dev)
+        unknown = int(opt.label_nc)
+        label_tag, orient_mask = label_tag.to(dev), orient_mask.to(dev)
+        data = {"label_ref": self._map(label_ref, crop, mode=1, unknown_label=unknown),
+                "label_tag": self._map(label_tag, crop, mode=1, unknown_label=unknown), "instance": torch.tensor(0)}
+        label_t = data["label_tag"]
+        if ig and not getattr(opt, "no_orientation", False):                    # :106-112: the picture of orient_ref under ITS mask
+            rgb = orient_to_rgb_u8(orient_ref.to(dev), orient_mask, self.table)
+            data["orient_rgb"] = self._map(rgb, crop, mode=2, mul=label_t)
+        else:
+            data["orient_rgb"] = torch.tensor(0)
+        if not ig:
+            data["hole"] = torch.tensor(0)
+        elif same_orient:                                                       # :116-120
+            t = torch.tensor([self.rng.uniform(0.5, 1.2) for _ in range(n)], dtype=torch.float64)
+            u = torch.tensor([self.rng.random() for _ in range(n)], dtype=torch.float64)
+            data["hole"] = self._map(generate_hole_u8(label_tag, orient_mask, t, u), crop, mode=1)
+        else:                                                                   # :122: label_tag - orient_mask * label_tag
+            data["hole"] = label_t - self._map(orient_mask, crop, mode=1, unknown_label=unknown, mul=label_t)
+        data["noise"] = generate_noise(n, self.crop_size, dev, self.generator)
+        data["image_ref"] = self._image(image_ref, crop)
+        data["image_tag"] = self._image(image_tag, crop)
+        data["orient"] = self._map(orient_tag, crop, mode=1)
+        return data
+
+    def demo_batch(self, *, label_ref, label_tag, mask_orient, orient_ref, image_ref, image_tag, mask_stroke=None,
+                   mask_hole=None) -> Dict[str, torch.Tensor]:
+        """demo_inference_dataLoad (base_dataset.py:162-276); the keys it returns, except `path`.  Its `orient_stroke` argument
+        (demo.py:325-326) is derived here from mask_stroke; mask_hole, the dilated stroke (demo.py:323-324), stays the caller's."""
+        opt, dev = self.opt, self.device
+        self._check_options("demo_batch")
+        if getattr(opt, "expand_tag_mask", False):
+            raise NotImplementedError("demo_batch: expand_tag_mask (a 25 x 25 cv2.dilate of the target mask) is not implemented")
+        if (mask_stroke is None) != (mask_hole is None):
+            raise ValueError("mask_stroke and mask_hole are given together (the stroke and its dilation), or neither")
+        label_tag = _decoded(label_tag, "label_tag", 1)
+        n = label_tag.shape[0]
+        label_ref, mask_orient, orient_ref = (_decoded(t, k, 1, n) for k, t in (
+            ("label_ref", label_ref), ("mask_orient", mask_orient), ("orient_ref", orient_ref)))
+        image_ref, image_tag = _decoded(image_ref, "image_ref", 3, n), _decoded(image_tag, "image_tag", 3, n)
+        _same_size({"mask_orient": mask_orient, "orient_ref": orient_ref})       # trans_orient_to_rgb (:207)
+        if mask_stroke is not None:
+            mask_stroke, mask_hole = _decoded(mask_stroke, "mask_stroke", 1, n), _decoded(mask_hole, "mask_hole", 1, n)
+            _same_size({"mask_stroke": mask_stroke, "mask_hole": mask_hole})
+        crop_h = self._window(n)
+        crop = crop_h.to(dev)
+        unknown = int(opt.label_nc)
+        mask_orient = mask_orient.to(dev)
+        data = {"label_ref": self._map(label_ref, crop, mode=1, unknown_label=unknown),
+                "label_tag": self._map(label_tag, crop, mode=1, unknown_label=unknown), "instance": torch.tensor(0)}
+        label_t = data["label_tag"]
+        rgb = orient_to_rgb_u8(orient_ref.to(dev), mask_orient, self.table)
+        data["orient_rgb"] = self._map(rgb, crop, mode=2, mul=label_t)
+        data["orient_rgb_mask"] = self._map(mask_orient, crop, mode=1, unknown_label=unknown, mul=label_t)           # :211
+        if mask_stroke is None:
+            data["hole"] = label_t - data["orient_rgb_mask"]                    # :216
+            data["orient_stroke"], data["mask_stroke"] = torch.tensor(0), torch.tensor(0)
+        else:
+            yt, xt = self._tabs_for(mask_stroke.shape[1], mask_stroke.shape[2])
+            data.update(stroke_inputs(mask_stroke.to(dev), label_t, mask_hole, crop=crop_h, ytab=yt, xtab=xt))
+        data["noise"] = generate_noise(n, self.crop_size, dev, self.generator)
+        data["image_ref"] = self._image(image_ref, crop)
+        data["image_tag"] = self._image(image_tag, crop)
+        data["orient"] = self._map(orient_ref, crop, mode=1)                    # :259: the demo's orientation is the reference's
+        return data
+
+
+def inference_batch(opt, *, image_ref, image_tag, label_ref, label_tag, orient_tag, orient_ref, orient_mask, same_orient,
+                    rng: Optional[_random.Random] = None, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+    """single_inference_dataLoad (base_dataset.py:49-160) for decoded uint8 maps on any device ([H,W] / [H,W,3], or with a leading
+    batch dimension): DeviceInputPipeline.inference_batch on a pipeline of its own.  A caller that loads batch after batch keeps
+    one pipeline and calls its method: the index tables are then built once."""
+    dev = _loader_device((label_tag, image_tag, image_ref))
+    return DeviceInputPipeline(opt, dev, rng=rng, generator=generator).inference_batch(
+        image_ref=image_ref, image_tag=image_tag, label_ref=label_ref, label_tag=label_tag, orient_tag=orient_tag, orient_ref=orient_ref,
+        orient_mask=orient_mask, same_orient=same_orient)
+
+
+def demo_batch(opt, *, label_ref, label_tag, mask_orient, orient_ref, image_ref, image_tag, mask_stroke=None, mask_hole=None,
+               rng: Optional[_random.Random] = None, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+    """demo_inference_dataLoad (base_dataset.py:162-276) for decoded uint8 maps on any device: DeviceInputPipeline.demo_batch on a
+    pipeline of its own (an interactive caller keeps one pipeline and calls its method)."""
+    dev = _loader_device((label_tag, image_tag, image_ref))
+    return DeviceInputPipeline(opt, dev, rng=rng, generator=generator).demo_batch(
+        label_ref=label_ref, label_tag=label_tag, mask_orient=mask_orient, orient_ref=orient_ref, image_ref=image_ref, image_tag=image_tag,
+        mask_stroke=mask_stroke, mask_hole=mask_hole)
+
+
