@@ -8,6 +8,9 @@
 // overlapping windows (16 taps), not by MFMA -- there is nothing to feed a matrix core with.
 // Results: same products and fp32 accumulation as the tap-list kernel in a different order, bias, activation, one
 // rounding to the storage type.
+// The wave-per-pixel body fetches every input pixel from L2 once per tap (16x for the 4x4 heads: 77 us per launch, 0.5 TB/s of
+// the 36 MB a launch has to read).  Stride-1 tap sets inside a 4x4 window (the heads) take conv_dot_tiled_kernel instead: a
+// workgroup owns 8 x 8 outputs and stages their 11 x 11 input patch once, so a pixel is read about twice.
 #include "mg_conv_common.h"
 #include "mg_launch.h"
 
@@ -99,6 +102,171 @@ __global__ __launch_bounds__(256) void conv_dot_kernel(const ConvK d)
             }
         }
     }
+}
+
+
+// ---- stride-1 windows of at most 4 x 4 taps: an 8 x 8 output tile per workgroup ------------------------------------------------------------
+// The input patch (8 + 3)^2 pixels goes through LDS in channel slices of 16 pieces of 16 bytes (128 bf16 / 64 fp32 channels: 31 KB), with
+// the slice of the weights beside it ([window position][co][piece], zeros where the tap list has no tap: no branch in the loop).  The
+// next slice is fetched into registers before the current one is consumed.  Thread = (strip of 4 consecutive outputs of one row, piece):
+// per window row it reads its 4 weight pieces and the 7 input pieces the strip's 4 x 4 products need (11 LDS reads for 16 piece
+// products), accumulates in fp32 registers across the slices, and the 16 piece lanes of a strip are summed with a shuffle tree at the
+// end.  Then the route's epilogue: bias, residual, activation, one rounding.
+constexpr int DTL_T = 8, DTL_WIN = 4, DTL_P = DTL_T + DTL_WIN - 1, DTL_PIECES = 16;
+constexpr int DTL_HPT = (DTL_P * DTL_P * DTL_PIECES + 255) / 256;              // 8 patch pieces per thread
+constexpr int DTL_PATCH_BYTES = DTL_P * DTL_P * DTL_PIECES * 16;               // 30976
+
+template <typename T>
+__device__ __forceinline__ void dot_unpack(const uint4 u, float (&v)[16 / sizeof(T)])
+{
+    const unsigned uu[4] = {u.x, u.y, u.z, u.w};
+    if constexpr (sizeof(T) == 2) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { v[2 * j] = __uint_as_float(uu[j] << 16); v[2 * j + 1] = __uint_as_float(uu[j] & 0xffff0000u); }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = __uint_as_float(uu[j]);
+    }
+}
+
+template <typename T, int NCO>
+__global__ __launch_bounds__(256) void conv_dot_tiled_kernel(const ConvK d, const int dy0, const int dx0, const int tiles_x, const int tiles_y)
+{
+    constexpr int EPL = 16 / (int)sizeof(T), SL = DTL_PIECES * EPL;            // channels per slice
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint4* const psm = reinterpret_cast<uint4*>(smem);                         // [pixel][piece]
+    uint4* const wsm = reinterpret_cast<uint4*>(smem + DTL_PATCH_BYTES);       // [window position][co][piece]
+    __shared__ int tmap[DTL_WIN * DTL_WIN];                                    // window position -> tap, or -1
+    const int tid = threadIdx.x, piece = tid & 15, strip = tid >> 4;
+    const int row = strip >> 1, xs = (strip & 1) * 4;
+    int b = blockIdx.x;
+    const int tx = b % tiles_x; b /= tiles_x;
+    const int ty = b % tiles_y, n = b / tiles_y;
+    const int y0 = ty * DTL_T, x0 = tx * DTL_T;
+    if (tid < DTL_WIN * DTL_WIN) tmap[tid] = -1;
+    __syncthreads();
+    if (tid < d.ntaps) tmap[((int)(short)(d.tap[tid] & 0xffff) - dy0) * DTL_WIN + (d.tap[tid] >> 16) - dx0] = tid;
+    __syncthreads();
+    const T* __restrict__ In = reinterpret_cast<const T*>(d.in);
+    const T* __restrict__ Wt = reinterpret_cast<const T*>(d.wt);              // packed image [tap][CoutP][Cin]
+
+    // this thread's pieces of a slice: patch pixels (zero outside the image) and weights, as element offsets (-1: zero)
+    const T* __restrict__ In_n = In + (size_t)n * d.Hin * d.Win * d.Cin;
+    int psrc[DTL_HPT], wsrc[NCO];
+#pragma unroll
+    for (int q = 0; q < DTL_HPT; ++q) {
+        const int i = tid + q * 256, px = i >> 4;
+        const int hy = px / DTL_P, hx = px - hy * DTL_P;
+        const int gy = y0 + dy0 + hy, gx = x0 + dx0 + hx;
+        psrc[q] = (px < DTL_P * DTL_P && (unsigned)gy < (unsigned)d.Hin && (unsigned)gx < (unsigned)d.Win) ? (gy * d.Win + gx) * d.Cin + piece * EPL : -1;
+    }
+#pragma unroll
+    for (int q = 0; q < NCO; ++q) {                                            // 16 window positions x NCO x 16 pieces = NCO x 256
+        const int i = tid + q * 256, pos = (i >> 4) / NCO, co = (i >> 4) - pos * NCO;
+        const int t = tmap[pos];
+        wsrc[q] = t >= 0 ? (t * d.CoutP + co) * d.Cin + piece * EPL : -1;
+    }
+    uint4 pv[DTL_HPT], wv[NCO];
+    auto fetch = [&](int c0) {
+#pragma unroll
+        for (int q = 0; q < DTL_HPT; ++q) pv[q] = psrc[q] >= 0 ? *reinterpret_cast<const uint4*>(In_n + psrc[q] + c0) : make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+        for (int q = 0; q < NCO; ++q) wv[q] = wsrc[q] >= 0 ? *reinterpret_cast<const uint4*>(Wt + wsrc[q] + c0) : make_uint4(0u, 0u, 0u, 0u);
+    };
+    float acc[NCO][4];
+#pragma unroll
+    for (int co = 0; co < NCO; ++co)
+#pragma unroll
+        for (int o = 0; o < 4; ++o) acc[co][o] = 0.f;
+
+    fetch(0);
+    for (int c0 = 0; c0 < d.Cin; c0 += SL) {
+        if (c0) __syncthreads();                                               // the previous slice has been consumed
+#pragma unroll
+        for (int q = 0; q < DTL_HPT; ++q) if (tid + q * 256 < DTL_P * DTL_P * DTL_PIECES) psm[tid + q * 256] = pv[q];
+#pragma unroll
+        for (int q = 0; q < NCO; ++q) wsm[tid + q * 256] = wv[q];
+        __syncthreads();
+        if (c0 + SL < d.Cin) fetch(c0 + SL);
+#pragma unroll 1
+        for (int ky = 0; ky < DTL_WIN; ++ky) {                                 // (not unrolled: the scheduler hoisted every LDS read of a slice and spilled)
+            const uint4* prow = psm + ((row + ky) * DTL_P + xs) * DTL_PIECES + piece;
+#pragma unroll
+            for (int co = 0; co < NCO; ++co) {
+                float w[DTL_WIN][EPL];
+#pragma unroll
+                for (int kx = 0; kx < DTL_WIN; ++kx) dot_unpack<T>(wsm[((ky * DTL_WIN + kx) * NCO + co) * DTL_PIECES + piece], w[kx]);
+#pragma unroll
+                for (int xi = 0; xi < DTL_T / 2 + DTL_WIN - 1; ++xi) {
+                    float xv[EPL];
+                    dot_unpack<T>(prow[xi * DTL_PIECES], xv);
+#pragma unroll
+                    for (int kx = 0; kx < DTL_WIN; ++kx) {
+                        const int o = xi - kx;
+                        if (o < 0 || o >= 4) continue;
+                        float sum = acc[co][o];
+#pragma unroll
+                        for (int j = 0; j < EPL; ++j) sum = fmaf(xv[j], w[kx][j], sum);
+                        acc[co][o] = sum;
+                    }
+                }
+            }
+        }
+    }
+    // the 16 piece lanes of a strip hold partial sums of the same 4 x nco outputs
+#pragma unroll
+    for (int co = 0; co < NCO; ++co) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            float v = acc[co][o];
+#pragma unroll
+            for (int off = 8; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+            acc[co][o] = v;
+        }
+    }
+    const int jy = y0 + row;
+    if (piece == 0 && jy < d.Hj) {
+        T* __restrict__ Out = reinterpret_cast<T*>(d.out);
+        const T* __restrict__ Res = reinterpret_cast<const T*>(d.resid);
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            const int jx = x0 + xs + o;
+            if (jx >= d.Wj) break;
+            const size_t ob = ((size_t)(n * d.Hout + jy * d.osy + d.ooy) * d.Wout + jx * d.osx + d.oox) * d.Cout;
+#pragma unroll
+            for (int co = 0; co < NCO; ++co) {
+                float v = acc[co][o] + (d.bias ? d.bias[co] : 0.f);
+                if (Res) v += ET<T>::load1(Res + ob + co);
+                ET<T>::store1(Out + ob + co, mg_act(v, d.act, d.slope));
+            }
+        }
+    }
+}
+
+struct DotTileGeom { int dy0, dx0, tiles_x, tiles_y; long ntiles; };
+
+// stride 1, distinct taps inside one 4 x 4 window, whole channel slices
+bool dot_tiled_geom(const ConvK& k, int dtype, DotTileGeom& g)
+{
+    const int sl = DTL_PIECES * (dtype == MG_BF16 ? 8 : 4);
+    if (k.isy != 1 || k.isx != 1 || k.ntaps < 1 || k.ntaps > DTL_WIN * DTL_WIN || k.Cin % sl != 0) return false;
+    int dy0 = 127, dx0 = 127, dy1 = -128, dx1 = -128;
+    for (int t = 0; t < k.ntaps; ++t) {
+        const int dy = (int)(short)(k.tap[t] & 0xffff), dx = k.tap[t] >> 16;
+        dy0 = dy < dy0 ? dy : dy0; dy1 = dy > dy1 ? dy : dy1; dx0 = dx < dx0 ? dx : dx0; dx1 = dx > dx1 ? dx : dx1;
+    }
+    if (dy1 - dy0 >= DTL_WIN || dx1 - dx0 >= DTL_WIN) return false;
+    if ((long)k.Hin * k.Win * k.Cin > 0x7fffffffL || (long)k.ntaps * k.CoutP * k.Cin > 0x7fffffffL) return false;      // 32-bit element offsets inside an image
+    unsigned seen = 0;
+    for (int t = 0; t < k.ntaps; ++t) {
+        const unsigned bit = 1u << ((((int)(short)(k.tap[t] & 0xffff)) - dy0) * DTL_WIN + (k.tap[t] >> 16) - dx0);
+        if (seen & bit) return false;
+        seen |= bit;
+    }
+    g.dy0 = dy0; g.dx0 = dx0;
+    g.tiles_x = (k.Wj + DTL_T - 1) / DTL_T; g.tiles_y = (k.Hj + DTL_T - 1) / DTL_T;
+    g.ntiles = (long)k.N * g.tiles_x * g.tiles_y;
+    return g.ntiles <= 0x7fffffffL;
 }
 
 
@@ -248,6 +416,20 @@ bool conv_dot_applies(const ConvK& k, int dtype, int epilogue)
 int launch_conv_dot(ConvK& k, int dtype, hipStream_t st)
 {
     const int esz = dtype == MG_BF16 ? 2 : 4;
+    DotTileGeom g;
+    if (dot_tiled_geom(k, dtype, g)) {
+        const size_t tlds = DTL_PATCH_BYTES + (size_t)DTL_WIN * DTL_WIN * k.Cout * DTL_PIECES * 16;       // 35 KB for one output channel
+        mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)g.ntiles), dim3(256), tlds, st, k, g.dy0, g.dx0, g.tiles_x, g.tiles_y); };
+            switch (k.Cout) {                           // 1 .. DOT_MAXCO (conv_dot_applies)
+                case 1: go(conv_dot_tiled_kernel<T, 1>); break;
+                case 2: go(conv_dot_tiled_kernel<T, 2>); break;
+                case 3: go(conv_dot_tiled_kernel<T, 3>); break;
+                default: go(conv_dot_tiled_kernel<T, 4>); break;
+            } });
+        MG_CHECK_LAUNCH("mg_conv_taps(dot, tiled)");
+        return MG_OK;
+    }
     const size_t lds = (size_t)k.ntaps * k.Cout * k.Cin * esz;
     long nblk = ((long)k.ngemm + 3) / 4;
     if (nblk > 256 * 8) nblk = 256 * 8;                                        // persistent: 8 workgroups per CU at most

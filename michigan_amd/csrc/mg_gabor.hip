@@ -27,63 +27,100 @@ __device__ __forceinline__ float gray_at(const T* img, int n, int y, int x, int 
     return GR * ((r + 1.f) * 0.5f * 255.f) + GG * ((g + 1.f) * 0.5f * 255.f) + GB * ((b + 1.f) * 0.5f * 255.f);
 }
 
+// Persistent workgroups: the 37 KB bank is staged once and a workgroup walks tiles blockIdx.x, + gridDim.x, ...; the next tile's gray
+// patch is fetched into registers before the current tile's MFMAs.  Wave w owns tile rows 4w .. 4w+3 (one MFMA column tile = the 32
+// pixels of one row) and keeps all four accumulator sets: the tap loop is outside, so one weight read feeds four MFMAs and four
+// independent chains are in flight.  (The first version re-staged the bank per 16 x 32 pixels and ran one chain with two ds_read_b32
+// and a k / 17 per MFMA: 66 of 157 TFLOP/s.)
+// K step s covers taps k = 2s (lanes 0..31) and 2s + 1 (lanes 32..63), k = ky * 17 + kx.  Two kernel rows are 34 taps = 17 steps, so the
+// steps are walked as a (row pair j, step i) nest in which every LDS address is a lane constant plus an immediate:
+//   i < 8: (ky, kx) = (2j, 2i + hi)     i = 8: hi ? (2j + 1, 0) : (2j, 16)     i > 8: (2j + 1, 2i - 17 + hi)
+// and the last row (ky = 16) is nine steps whose final one pairs tap 288 with the zero-weight pad tap 289 (read at the pixel itself, as
+// before).  Every output's accumulation chain sees the same instruction with the same operands in the same order as in the first version:
+// conf and idx keep their bits.
 template <typename T>
 __global__ __launch_bounds__(256) void gabor_fwd_kernel(const T* __restrict__ img, const float* __restrict__ bank,
                                                         float* __restrict__ conf, uint8_t* __restrict__ idx,
-                                                        int N, int H, int W, int C, int tiles_x, int tiles_y)
+                                                        int N, int H, int W, int C, int tiles_x, int tiles_y, int ntiles)
 {
     __shared__ float patch[PGH * PGW];                 // 6 KiB
     __shared__ float wts[NF * (NTAP + 1)];             // 32 x 290 (tap 289 = 0), 36.25 KiB
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
-    int t = blockIdx.x;
-    const int tx = t % tiles_x; t /= tiles_x;
-    const int ty = t % tiles_y;
-    const int n = t / tiles_y;
-    const int y0 = ty * TGH, x0 = tx * TGW;
+    constexpr int PPT = PGH * PGW / 256;               // 6 patch pixels per thread
 
-    for (int i = tid; i < PGH * PGW; i += 256) {
-        const int py = i / PGW, px = i - py * PGW;
-        patch[i] = gray_at(img, n, y0 + py - KR, x0 + px - KR, H, W, C);
-    }
     for (int i = tid; i < NF * (NTAP + 1); i += 256) {
         const int f = i / (NTAP + 1), k = i - f * (NTAP + 1);
         wts[i] = k < NTAP ? bank[f * NTAP + k] : 0.f;
     }
-    __syncthreads();
+    float nxt[PPT];
+    auto fetch = [&](int tile) {
+        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
+#pragma unroll
+        for (int q = 0; q < PPT; ++q) {
+            const int i = tid + q * 256, py = i / PGW, px = i - py * PGW;
+            nxt[q] = gray_at(img, n, ty * TGH + py - KR, tx * TGW + px - KR, H, W, C);
+        }
+    };
+    if ((int)blockIdx.x < ntiles) fetch(blockIdx.x);
 
-    // wave w owns tile rows 4w .. 4w+3; one MFMA column tile = the 32 pixels of one row
-    for (int rr = 0; rr < 4; ++rr) {
-        const int row = wave * 4 + rr;
-        f32x16_t acc;
+    const float* const pa = wts + l31 * (NTAP + 1) + hi;                      // + 2s
+    const float* const pb = patch + (wave * 4) * PGW + l31 + hi;              // the regular steps
+    const float* const pb8 = patch + (wave * 4) * PGW + l31 + 16 + hi * 32;   // step 8 of a row pair
+    const float* const pbl = patch + (wave * 4) * PGW + l31 + (hi ? 0 : 16 * PGW + 16);   // the last step: tap 288 | the pad tap
+
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
+        const int y0 = ty * TGH, x0 = tx * TGW;
+        __syncthreads();                               // the previous tile's MFMAs have read the patch
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        // K step s covers taps 2s (hi = 0) and 2s+1 (hi = 1)
-        for (int s = 0; s < (NTAP + 1) / 2; ++s) {
-            const int k = 2 * s + hi;
-            const int ky = k / KS, kx = k - ky * KS;                       // k = 289 -> ky = 17: weight is 0, address stays inside the patch? no -> clamp
-            const float a = wts[l31 * (NTAP + 1) + k];
-            const int pyy = (k < NTAP) ? row + ky : row;
-            const int pxx = (k < NTAP) ? l31 + kx : l31;
-            const float b = patch[pyy * PGW + pxx];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-        }
-        // lane holds, for pixel column l31, filters (r&3) + 8*(r>>2) + 4*hi; clamp < 0 to 0, first arg-max
-        float best = -1.f; int bi = 0;
+        for (int q = 0; q < PPT; ++q) patch[tid + q * 256] = nxt[q];
+        __syncthreads();
+        if (tile + (int)gridDim.x < ntiles) fetch(tile + gridDim.x);
+
+        f32x16_t acc[4];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int f = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            const float v = fmaxf(acc[r], 0.f);
-            if (v > best || (v == best && f < bi)) { best = v; bi = f; }
+        for (int rr = 0; rr < 4; ++rr)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[rr][r] = 0.f;
+#pragma unroll 1
+        for (int j = 0; j < 8; ++j) {
+            const float* const a_j = pa + j * 34;
+            const float* const b_j = pb + j * 2 * PGW, * const b8_j = pb8 + j * 2 * PGW;
+#pragma unroll
+            for (int i = 0; i < 17; ++i) {
+                const float a = a_j[2 * i];
+                const float* const b = i == 8 ? b8_j : b_j + (i < 8 ? 2 * i : PGW + 2 * i - 17);
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) acc[rr] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[rr * PGW], acc[rr], 0, 0, 0);
+            }
         }
-        const float ob = __shfl_xor(best, 32, 64);
-        const int oi = __shfl_xor(bi, 32, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-        const int y = y0 + row, x = x0 + l31;
-        if (hi == 0 && y < H && x < W) {
-            const size_t o = (size_t)(n * H + y) * W + x;
-            conf[o] = best;
-            idx[o] = (uint8_t)bi;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {                  // ky = 16
+            const float a = pa[2 * (136 + i)];
+            const float* const b = i == 8 ? pbl : pb + 16 * PGW + 2 * i;
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) acc[rr] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[rr * PGW], acc[rr], 0, 0, 0);
+        }
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            // lane holds, for pixel column l31, filters (r&3) + 8*(r>>2) + 4*hi; clamp < 0 to 0, first arg-max
+            float best = -1.f; int bi = 0;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int f = (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const float v = fmaxf(acc[rr][r], 0.f);
+                if (v > best || (v == best && f < bi)) { best = v; bi = f; }
+            }
+            const float ob = __shfl_xor(best, 32, 64);
+            const int oi = __shfl_xor(bi, 32, 64);
+            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+            const int y = y0 + wave * 4 + rr, x = x0 + l31;
+            if (hi == 0 && y < H && x < W) {
+                const size_t o = (size_t)(n * H + y) * W + x;
+                conf[o] = best;
+                idx[o] = (uint8_t)bi;
+            }
         }
     }
 }
@@ -149,9 +186,11 @@ extern "C" int mg_gabor_argmax_fwd(const void* img, const float* bank, float* co
     MG_GABOR_CHECK("mg_gabor_argmax_fwd");
     MG_CHECK_ARG(img && bank && conf && idx, "mg_gabor_argmax_fwd: null pointer");
     const int tx = (W + TGW - 1) / TGW, ty = (H + TGH - 1) / TGH;
+    MG_CHECK_ARG((int64_t)N * tx * ty <= 0x7fffffff, "mg_gabor_argmax_fwd: too many tiles");
+    const int ntiles = N * tx * ty;                     // two persistent workgroups per CU (42 KB of LDS each)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
-        hipLaunchKernelGGL(gabor_fwd_kernel<T>, dim3(N * tx * ty), dim3(256), 0, st, (const T*)img, bank, conf, idx, N, H, W, C, tx, ty); });
+        hipLaunchKernelGGL(gabor_fwd_kernel<T>, dim3(ntiles < 512 ? ntiles : 512), dim3(256), 0, st, (const T*)img, bank, conf, idx, N, H, W, C, tx, ty, ntiles); });
     MG_CHECK_LAUNCH("mg_gabor_argmax_fwd");
     return MG_OK;
 }

@@ -16,7 +16,7 @@
 
 namespace {
 
-constexpr int PACK_PER_BLOCK = 1024;      // destination elements per workgroup (4 per thread)
+constexpr int PACK_PER_BLOCK = 4096;      // mode 2: elements per workgroup (16 per thread, all loads in flight before the first store)
 constexpr int K1_ROWS = 128;              // rows of W per W^T u partial block (32: the per-layer finish walked 32 partials per column, 53 us)
 constexpr int K1_COLS = 1024;             // columns per block: four per thread, 16-byte loads
 constexpr int K3_ROWS = 4;                // rows of W per W v block (one wave each)
@@ -30,89 +30,206 @@ __device__ __forceinline__ int row_to_co2(int r, int cout, bool two, int& which)
     return co < cout ? co : -1;
 }
 
-// Tile = 4 destination rows x 64 destination columns x all T taps.  Destination element (t, r, c) of a GEMM image comes from
+// Destination element (t, r, c) of a GEMM image comes from
 //   mode 0: W[co(r)][ci = c][t]      mode 1: W[co(c)][ci = r][t]       (co() = identity, or the gamma|beta row interleave)
 // The reference layout has t fastest, so a gather by destination index (what the per-image pack_kernel does) touches every
 // 64-byte line of W once per tap, T blocks apart: with 438 MB of generator weights that is T re-reads from HBM (the first batched
-// version measured 1.5 TB/s of useful bytes).  Here a workgroup reads its sources as contiguous runs (mode 0: 64*T floats per row,
-// mode 1: 4*T floats per column), transposes through LDS (pitch T|1: conflict-free for T = 1, 9, 16, 49) and writes
-// 128-byte destination rows: every byte of W is read once.
-constexpr int PK_ROWS = 4, PK_COLS = 64, PK_MAXT = 49;
-// LDS: the 64 columns of a tile go through in sub-tiles of SC columns, SC = 64 for T <= 16 and 16 for the 7x7 window, so that the
-// buffer is 17 KiB instead of the 50 KiB a full 7x7 tile needs (one 7x7 layer in the table used to cap EVERY workgroup of the
-// launch at 3 per CU; with 8 per CU the 109 M generator weights re-pack in well under half the time, profiles/r02_pack_ab.txt).
-constexpr int PK_LDS_FLOATS = PK_ROWS * 64 * 17;                 // >= 4 x 64 x (16 | 1) and >= 4 x 16 x (49 | 1) = 3200
+// version measured 1.5 TB/s of useful bytes).  Here a workgroup reads its sources as contiguous runs (mode 0: one run of CW*T
+// floats per row, mode 1: one run of R*T floats per column), transposes through LDS and writes whole destination rows: every
+// byte of W is read once.
+//
+// Tile = R destination rows x CW destination columns x all T taps:
+//   CW = 128 where the image is wider than 64 columns (a wave's 16-byte stores then cover whole 256-byte bf16 runs), else 64;
+//   R * CW = 512 (2048 for T = 1, where a 512-element tile is two elements per thread), so a T <= 16 tile is 18-32 KB of W.
+// A thread issues all its loads (up to eight 16-byte ones) before the first LDS write.  The first version moved 9 KB per
+// workgroup with 4-byte loads and stores and a barrier pair per sub-tile, and sat at 2.9 TB/s (latency-bound).
+// 16-byte loads need every run to start on a 16-byte boundary: cin * T % 4 == 0 and aligned tensors (a 3-channel layer has rows
+// of 27 floats: 4-byte loads, eight in flight); 16-byte stores need cols_p % 8 == 0 and an aligned image, else column pairs.
+// LDS holds the tile in destination order, [t][r][c] with a plane pitch of R*SC + 4 floats, so that a store item (eight
+// consecutive columns of one (tap, row)) is two ds_read_b128.  T > 16 (5x5, 7x7) goes through in sub-tiles of SC = 32 columns
+// x 4 rows, which keeps the buffer at 33 KB for every window: four workgroups per CU (a 50 KiB 7x7 tile capped EVERY workgroup
+// of the launch at 3 per CU, profiles/r02_pack_ab.txt).
+constexpr int PK_MAXT = 49;
+constexpr int PK_LDS_FLOATS = 16 * (512 + 4);                    // T <= 16: 16 planes; T = 1: 2052; T = 49: 49 x 132 = 6468
+__host__ __device__ constexpr int pk_cw(int cols_p) { return cols_p > 64 ? 128 : 64; }
+__host__ __device__ constexpr int pk_rows(int taps, int cw) { return taps == 1 ? 2048 / cw : taps <= 16 ? 512 / cw : 4; }
+__host__ __device__ constexpr int pk_sub(int taps, int cw) { return taps <= 16 ? cw : 32; }
 
-__global__ __launch_bounds__(256) void pack_weights_kernel(const mg_pack_job* __restrict__ jobs, const int32_t* __restrict__ block_job)
+// TT = 0: any window (run-time divisions); the windows the networks use are instantiated with constant divisors
+template <int TT, int CW>
+__device__ __forceinline__ void pack_tile(const mg_pack_job& j, const int rel, float* __restrict__ tile)
 {
-    __shared__ float tile[PK_LDS_FLOATS];
+    const int T = TT ? TT : j.taps;
+    const int R = pk_rows(T, CW), SC = pk_sub(T, CW), plane = R * SC + 4;
+    const int tid = threadIdx.x;
+    const bool two = j.w1 != nullptr, m0 = j.mode == 0;
+    const int cblocks = (j.cols_p + CW - 1) / CW;
+    const int r0 = (rel / cblocks) * R, cb0 = (rel % cblocks) * CW;
+    const float sg = j.sigma ? j.sigma[0] : 1.f;
+    // a sub-tile is `nrun` contiguous source runs with room for L floats each: mode 0 one per row (SC columns x T),
+    // mode 1 one per column (R rows x T).  Element e of run u is (x = e / T, t = e % T) -> (r, c) = mode 0 ? (u, x) : (x, u)
+    const int nrun = m0 ? R : SC, L = (m0 ? SC : R) * T;
+    const bool vec_ld = ((j.cin * T) & 3) == 0 && (((uintptr_t)j.w0 | (uintptr_t)j.w1) & 15) == 0;
+    const bool vec_st = (j.cols_p & 7) == 0 && ((uintptr_t)j.dst & 15) == 0;
+    for (int sc = 0; sc < CW; sc += SC) {
+        const int c0 = cb0 + sc;
+        if (c0 >= j.cols_p) break;                               // uniform
+        if (sc) __syncthreads();                                 // the previous sub-tile has been stored
+        // source run u: its first element and how many of its L floats exist (the rest of the tile is zero padding)
+        auto run = [&](int u, int& valid) -> const float* {
+            int which = 0;
+            const int g = m0 ? r0 + u : c0 + u;                  // GEMM output-channel index
+            const int co = g < (m0 ? j.rows_p : j.cols_p) ? row_to_co2(g, j.cout, two, which) : -1;
+            const int ci0 = m0 ? c0 : r0;
+            valid = co >= 0 ? max(0, min(m0 ? SC : R, j.cin - ci0)) * T : 0;
+            return (which ? j.w1 : j.w0) + ((size_t)max(co, 0) * j.cin + ci0) * T;
+        };
+        if (vec_ld) {
+            const int L4 = L >> 2, items = nrun * L4;            // <= 2048 16-byte pieces
+            float4 v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int q = tid + k * 256;
+                v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (q < items) {
+                    const int u = q / L4, e = (q - u * L4) * 4;
+                    int valid;
+                    const float* src = run(u, valid);
+                    if (e < valid) v[k] = *reinterpret_cast<const float4*>(src + e);       // valid % 4 == 0
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int q = tid + k * 256;
+                if (q < items) {
+                    const int u = q / L4, e = (q - u * L4) * 4;
+                    int x = e / T, t = e - x * T;
+                    const float vv[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        tile[t * plane + (m0 ? u * SC + x : x * SC + u)] = vv[i];
+                        if (++t == T) { t = 0; ++x; }
+                    }
+                }
+            }
+        } else {
+            const int items = nrun * L;                          // <= 8192 floats: four rounds of eight loads in flight
+            for (int kb = 0; kb < 32 && kb * 256 < items; kb += 8) {
+                float v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const int q = tid + (kb + k) * 256;
+                    v[k] = 0.f;
+                    if (q < items) {
+                        const int u = q / L, e = q - u * L;
+                        int valid;
+                        const float* src = run(u, valid);
+                        if (e < valid) v[k] = src[e];
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const int q = tid + (kb + k) * 256;
+                    if (q < items) {
+                        const int u = q / L, e = q - u * L;
+                        const int x = e / T, t = e - x * T;
+                        tile[t * plane + (m0 ? u * SC + x : x * SC + u)] = v[k];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        // ---- store: eight consecutive destination columns of one (tap, row) per item -----------------------------------------------
+        const int g8 = SC >> 3, per_t = R * g8;                  // powers of two
+        for (int q = tid; q < T * per_t; q += 256) {
+            const int t = q / per_t, rem = q - t * per_t;
+            const int rr = rem / g8, cg = rem - rr * g8;
+            const int r = r0 + rr, c = c0 + cg * 8;
+            if (r >= j.rows_p || c >= j.cols_p) continue;
+            const float* p = tile + t * plane + rr * SC + cg * 8;
+            const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+            float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+            if (j.sigma) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = v[i] / sg;    // a true division, like torch
+            }
+            const size_t o = ((size_t)t * j.rows_p + r) * j.cols_p + c;
+            if (j.dtype == MG_BF16) {
+                uint16_t* d = reinterpret_cast<uint16_t*>(j.dst) + o;
+                if (vec_st) *reinterpret_cast<uint4*>(d) = make_uint4(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]), f2bf2(v[6], v[7]));
+                else {
+#pragma unroll
+                    for (int i = 0; i < 8; i += 2) if (c + i < j.cols_p) *reinterpret_cast<uint32_t*>(d + i) = f2bf2(v[i], v[i + 1]);     // cols_p is even
+                }
+            } else {
+                float* d = reinterpret_cast<float*>(j.dst) + o;
+                if (vec_st) {
+                    *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
+                    *reinterpret_cast<float4*>(d + 4) = make_float4(v[4], v[5], v[6], v[7]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 8; i += 2) if (c + i < j.cols_p) { float2 pv; pv.x = v[i]; pv.y = v[i + 1]; *reinterpret_cast<float2*>(d + i) = pv; }
+                }
+            }
+        }
+    }
+}
+
+template <int TT>
+__device__ __forceinline__ void pack_tile_w(const mg_pack_job& j, const int rel, float* __restrict__ tile)
+{
+    if (pk_cw(j.cols_p) == 128) pack_tile<TT, 128>(j, rel, tile);
+    else pack_tile<TT, 64>(j, rel, tile);
+}
+
+// four waves per SIMD = four workgroups per CU (what the LDS tile allows): 128 registers; 143 and three workgroups measured 14 % slower
+__global__ __launch_bounds__(256, 4) void pack_weights_kernel(const mg_pack_job* __restrict__ jobs, const int32_t* __restrict__ block_job)
+{
+    __shared__ __attribute__((aligned(16))) float tile[PK_LDS_FLOATS];
     const mg_pack_job& j = jobs[block_job[blockIdx.x]];
     const int rel = (int)((int64_t)blockIdx.x - j.first_block);
     const int tid = threadIdx.x;
     if (j.mode == 2) {                                           // fp32 copy of w0 / sigma, reference layout
         const int64_t total = (int64_t)j.cout * j.cin * j.taps, base = (int64_t)rel * PACK_PER_BLOCK;
         const float sg = j.sigma ? j.sigma[0] : 1.f;
+        float* const dst = reinterpret_cast<float*>(j.dst);
+        if ((((uintptr_t)j.w0 | (uintptr_t)j.dst) & 15) == 0) {  // (inside SpectralPlan's buffer the destination is only 4-byte aligned)
+            float4 v[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = base + (k * 256 + tid) * 4;
+                if (i + 4 <= total) v[k] = *reinterpret_cast<const float4*>(j.w0 + i);
+                else { v[k].x = i < total ? j.w0[i] : 0.f; v[k].y = i + 1 < total ? j.w0[i + 1] : 0.f; v[k].z = i + 2 < total ? j.w0[i + 2] : 0.f; v[k].w = 0.f; }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = base + (k * 256 + tid) * 4;
+                float4 o = v[k];
+                if (j.sigma) { o.x = o.x / sg; o.y = o.y / sg; o.z = o.z / sg; o.w = o.w / sg; }      // a true division, like torch
+                if (i + 4 <= total) *reinterpret_cast<float4*>(dst + i) = o;
+                else { if (i < total) dst[i] = o.x; if (i + 1 < total) dst[i + 1] = o.y; if (i + 2 < total) dst[i + 2] = o.z; }
+            }
+            return;
+        }
+        float v[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
             const int64_t i = base + k * 256 + tid;
-            if (i < total) reinterpret_cast<float*>(j.dst)[i] = j.sigma ? j.w0[i] / sg : j.w0[i];     // a true division, like torch
+            v[k] = i < total ? j.w0[i] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int64_t i = base + k * 256 + tid;
+            if (i < total) dst[i] = j.sigma ? v[k] / sg : v[k];
         }
         return;
     }
-    const bool two = j.w1 != nullptr;
-    const int T = j.taps, pitch = T | 1;
-    const int SC = T <= 16 ? 64 : 16;                            // sub-tile width (columns)
-    const int cblocks = (j.cols_p + PK_COLS - 1) / PK_COLS;
-    const int r0 = (rel / cblocks) * PK_ROWS, cb0 = (rel % cblocks) * PK_COLS;
-    const float sg = j.sigma ? j.sigma[0] : 1.f;
-    // store mapping: 4 rows x (SC/2 column pairs) x (128/SC tap phases)
-    const int pairs = SC >> 1, nphase = 64 / pairs;
-    const int rr_s = tid >> 6, cp = ((tid & 63) % pairs) * 2, th = (tid & 63) / pairs;
-    for (int sc = 0; sc < PK_COLS; sc += SC) {
-        const int c0 = cb0 + sc;
-        if (c0 >= j.cols_p) break;                               // uniform
-        if (sc) __syncthreads();                                 // the previous sub-tile has been stored
-        // ---- load: contiguous runs of the reference-layout source --------------------------------------------------------------
-        if (j.mode == 0) {
-            const int ncol = max(0, min(SC, j.cin - c0));        // source columns (ci) that exist; the rest of the tile is zero padding
-            for (int rr = 0; rr < PK_ROWS; ++rr) {
-                int which = 0;
-                const int co = (r0 + rr < j.rows_p) ? row_to_co2(r0 + rr, j.cout, two, which) : -1;
-                const float* src = (co >= 0 && ncol > 0) ? (which ? j.w1 : j.w0) + ((size_t)co * j.cin + c0) * T : nullptr;
-                const int run = src ? ncol * T : 0;
-                int c = tid / T, t = tid - c * T;
-                const int dc = 256 / T, dt = 256 - dc * T;
-                for (int e = tid; e < SC * T; e += 256) {
-                    tile[(rr * SC + c) * pitch + t] = e < run ? src[e] : 0.f;
-                    c += dc; t += dt;
-                    if (t >= T) { t -= T; ++c; }
-                }
-            }
-        } else {
-            const int nrow = min(PK_ROWS, j.cin - r0);           // source rows (ci) that exist
-            const int per = PK_ROWS * T;                         // one column's contiguous run: W[co][r0 .. r0+3][0 .. T)
-            for (int e = tid; e < SC * per; e += 256) {
-                const int cc = e / per, rem = e - cc * per;
-                const int rr = rem / T, t = rem - rr * T;
-                int which = 0;
-                const int co = (c0 + cc < j.cols_p) ? row_to_co2(c0 + cc, j.cout, two, which) : -1;
-                float v = 0.f;
-                if (co >= 0 && rr < nrow) v = (which ? j.w1 : j.w0)[((size_t)co * j.cin + r0) * T + rem];
-                tile[(rr * SC + cc) * pitch + t] = v;
-            }
-        }
-        __syncthreads();
-        // ---- store: rows of consecutive destination columns (2 per thread) -------------------------------------------------------
-        const int r = r0 + rr_s, c = c0 + cp;
-        if (r < j.rows_p && c < j.cols_p) {                      // cols_p is even (a multiple of 8)
-            for (int t = th; t < T; t += nphase) {
-                float v0 = tile[(rr_s * SC + cp) * pitch + t], v1 = tile[(rr_s * SC + cp + 1) * pitch + t];
-                if (j.sigma) { v0 = v0 / sg; v1 = v1 / sg; }
-                const size_t o = ((size_t)t * j.rows_p + r) * j.cols_p + c;
-                if (j.dtype == MG_BF16) reinterpret_cast<uint32_t*>(j.dst)[o >> 1] = f2bf2(v0, v1);
-                else { float2 pv; pv.x = v0; pv.y = v1; *reinterpret_cast<float2*>(reinterpret_cast<float*>(j.dst) + o) = pv; }
-            }
-        }
+    switch (j.taps) {
+        case 1:  pack_tile_w<1>(j, rel, tile); break;
+        case 9:  pack_tile_w<9>(j, rel, tile); break;
+        case 16: pack_tile_w<16>(j, rel, tile); break;
+        case 49: pack_tile_w<49>(j, rel, tile); break;
+        default: pack_tile_w<0>(j, rel, tile); break;
     }
 }
 
@@ -223,7 +340,8 @@ extern "C" int64_t mg_pack_job_blocks(int32_t mode, int32_t cout, int32_t cin, i
 {
     if (mode == 2) return cout > 0 && cin > 0 && taps > 0 ? ((int64_t)cout * cin * taps + PACK_PER_BLOCK - 1) / PACK_PER_BLOCK : -1;
     if ((mode != 0 && mode != 1) || rows_p <= 0 || cols_p <= 0 || (cols_p & 1) || taps <= 0 || taps > PK_MAXT) return -1;
-    return (int64_t)((rows_p + PK_ROWS - 1) / PK_ROWS) * ((cols_p + PK_COLS - 1) / PK_COLS);
+    const int cw = pk_cw(cols_p), r = pk_rows(taps, cw);
+    return (int64_t)((rows_p + r - 1) / r) * ((cols_p + cw - 1) / cw);
 }
 
 extern "C" int mg_pack_weights(const mg_pack_job* jobs_dev, int32_t njobs, const int32_t* block_job_dev, int32_t nblocks, void* stream)
