@@ -49,6 +49,16 @@ def _u8(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
+def upload(t: torch.Tensor, device) -> torch.Tensor:
+    """A small host tensor (a batch's draws, its sample indices) on `device` WITHOUT draining the stream: a plain `.to(device)` from
+    pageable memory synchronises the stream it copies on, so a loader that runs once per training step would wait for the whole
+    previous step at its first draw.  Through pinned memory the copy is one more entry of the stream."""
+    device = torch.device(device)
+    if device.type != "cuda" or t.is_cuda:
+        return t.to(device)
+    return t.pin_memory().to(device, non_blocking=True)
+
+
 def nearest_table(src: int, dst: int, device) -> Optional[torch.Tensor]:
     """Pillow's nearest-neighbour source index for each of `dst` output coordinates (None = identity)."""
     if src == dst:
@@ -416,7 +426,7 @@ class DeviceInputPipeline:
         image, label, orient = (t.to(dev) for t in (image, label, orient))
         image = self._resized(image)
         crop_h = self._window(n)
-        crop = crop_h.to(dev)
+        crop = upload(crop_h, dev)
         yt, xt = self._tab(label.shape[1]), self._tab(label.shape[2])
         unknown = int(opt.label_nc)
         label_t = crop_u8(label, crop, cs, mode=1, unknown_label=unknown, ytab=yt, xtab=xt)
@@ -429,7 +439,7 @@ class DeviceInputPipeline:
             data["orient_rgb"] = crop_u8(rgb, crop, cs, mode=2, ytab=yt, xtab=xt, mul=label_t)
             th = torch.tensor([self.rng.uniform(0.5, 1.2) for _ in range(n)], dtype=torch.float64)
             u = torch.tensor([self.rng.random() for _ in range(n)], dtype=torch.float64)
-            hole = generate_hole_u8(label, om, th, u)
+            hole = generate_hole_u8(label, om, upload(th, dev), upload(u, dev))
             data["hole"] = crop_u8(hole, crop, cs, mode=1, ytab=yt, xtab=xt)
         else:
             data["orient_rgb"], data["hole"] = torch.tensor(0), 0

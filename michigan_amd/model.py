@@ -137,7 +137,7 @@ class Pix2PixModel(nn.Module):
         out = {}
         for k in ("input_tag", "input_ref", "image_tag", "image_ref", "orient", "noise", "hole", "orient_rgb",
                   "orient_stroke", "mask_stroke", "orient_rgb_mask"):
-            if k in data:
+            if torch.is_tensor(data.get(k)):                # without use_ig the loader's `hole` is the reference's plain 0
                 out[k] = data[k].to(dev, non_blocking=True)
         for src, dst in (("label_tag", "input_tag"), ("label_ref", "input_ref")):
             if dst not in out:
@@ -499,6 +499,20 @@ class Pix2PixModel(nn.Module):
                 key = key[7:] if key.startswith("module.") else key
                 if key in own:
                     own[key].copy_(val)
+
+    def load_inpainting(self):
+        """util.load_inpainting_network / load_sinpainting_network (util/util.py:245-272): the frozen nets' pretrained files,
+        `<checkpoints_dir>/<name>/<ig_model_name>` (default InpaintingModel_gen.pth) into netIG and `<sig_model_name>` (default
+        SInpaintingModel_gen.pth) into netSIG, whichever is built.  Each file is {'generator': state_dict}, loaded with a strict
+        load_state_dict as there; a missing file raises FileNotFoundError with its path."""
+        for net, key, default in ((self.netIG, "ig_model_name", "InpaintingModel_gen.pth"),
+                                  (self.netSIG, "sig_model_name", "SInpaintingModel_gen.pth")):
+            if net is None:
+                continue
+            path = os.path.join(self.opt.checkpoints_dir, self.opt.name, getattr(self.opt, key, default))
+            if not os.path.isfile(path):
+                raise FileNotFoundError("in-painting network file %s does not exist" % path)
+            net.load_state_dict(torch.load(path, map_location="cpu")["generator"])
 
     def create_optimizers(self, opt, group=None):
         if os.environ.get("MG_DP_NO_GRAD") == "1":           # measurement switch: no gradient all-reduce
