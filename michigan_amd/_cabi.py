@@ -195,6 +195,13 @@ _PROTOS = {
     "mg_stroke_compose": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
     "mg_inpaint_finish": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp], _i32),
 }
+# include/michigan_hip/editing/mask_edit.h: the editing extension group (prefix mge_).  A table of its own: the group is outside the
+# versioned table above (MG_ABI_VERSION does not count it, oracle/cabi_emulator.py does not emulate it) until the change that next
+# owns the emulator moves it in.  Same calling convention: a status, the message behind mg_last_error.
+_EDIT_PROTOS = {
+    "mge_brush_u8": ([_vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
+    "mge_morph_u8": ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp], _i32),
+}
 EXPORTED_SYMBOLS = tuple(_PROTOS)              # the whole ABI: tests/test_cabi_host.py holds it to the headers and to the library's exports
 _NO_STATUS = {"mg_wgrad_det_workspace", "mg_norm_apply2_supported", "mg_grad_slot_blocks", "mg_pack_job_blocks", "mg_sn_layer_blocks", "mg_stats_workspace", "mg_sizeof_desc", "mg_abi_version", "mg_last_error", "mg_noise_field_len", "mg_bicubic_ksize",
               "mg_feat_moment_workspace"}
@@ -227,7 +234,7 @@ class HipBackend:
         # torch must already have loaded its libamdhip64 so that we bind to the same runtime.
         import torch  # noqa: F401
         self._lib = ctypes.CDLL(path)
-        for fn, (argtypes, restype) in _PROTOS.items():
+        for fn, (argtypes, restype) in list(_PROTOS.items()) + list(_EDIT_PROTOS.items()):
             f = getattr(self._lib, fn)          # AttributeError if a symbol is missing
             f.argtypes, f.restype = argtypes, restype
         if self._lib.mg_abi_version() != MG_ABI_VERSION:
@@ -236,7 +243,7 @@ class HipBackend:
             raise RuntimeError("ctypes mirror of the descriptor structs is out of sync with include/michigan_hip.h")
 
     def __getattr__(self, fn):
-        if fn not in _PROTOS:
+        if fn not in _PROTOS and fn not in _EDIT_PROTOS:
             raise AttributeError(fn)
         raw = getattr(self._lib, fn)
         if fn in _NO_STATUS:

@@ -15,6 +15,8 @@ same arithmetic runs here as HIP kernels of libmichigan_hip.so on u8 maps that w
     dense_orientation  cal_orientation.py: the uint8 orientation map itself, from an image and its hair mask
     stroke_to_orient   ui_util/cal_orient_stroke.py: the RGB-coded orientation picture of a drawn stroke mask
     stroke_inputs      demo_inference_dataLoad's orient_stroke / mask_stroke / hole tensors (base_dataset.py:214-238)
+    brush_u8           demo.py:431-435: the recorded pen segments painted onto a u8 map (the package's own capsule brush)
+    dilate_u8 / erode_u8 / stroke_hole   cv2.dilate / cv2.erode with any element; demo.py:323-324, the stroke widened into its hole
 
 `DeviceInputPipeline` strings them together into the `data` dict of pix2pix_dataset.py:178-188 (paired, and with image_ref /
 label_ref the unpaired stage's), `inference_batch` into single_inference_dataLoad's (base_dataset.py:49-160) and `demo_batch` into
@@ -252,7 +254,7 @@ def stroke_inputs(mask_stroke: torch.Tensor, label_tag: torch.Tensor, mask_hole:
                   xtab: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """The stroke entries of demo_inference_dataLoad's batch (base_dataset.py:214-238) at the size of label_tag [N,1,H,W] (the class
     index map as fp32): orient_stroke [N,3,H,W] = ToTensor(stroke picture) * label_tag, mask_stroke [N,1,H,W] = ToTensor(mask) * 255 *
-    label_tag and, when mask_hole is given (the caller dilates the stroke: demo.py:323-324), hole likewise.
+    label_tag and, when mask_hole is given (the dilated stroke, demo.py:323-324: `stroke_hole` makes it), hole likewise.
     Without `crop` the stroke mask has label_tag's size (the demo works at the crop size).  With `crop` (host int32 [N,3], the loader's
     window) the masks are at their stored size and take transform_label's resize (`ytab` / `xtab`: nearest_table of their height /
     width, None = identity) and crop; the stroke picture is made at the stored size, as the reference makes it (demo.py:325-326)."""
@@ -272,6 +274,140 @@ def stroke_inputs(mask_stroke: torch.Tensor, label_tag: torch.Tensor, mask_hole:
             raise ValueError(f"stroke_inputs: mask_hole {tuple(mask_hole.shape)} does not match the stroke mask's {tuple(m.shape)}")
         out["hole"] = crop_u8(hm, crop, (h, w), mode=1, ytab=ytab, xtab=xtab, mul=label)
     return out
+
+
+def ellipse_element(k_w: int, k_h: Optional[int] = None):
+    """cv2.getStructuringElement(cv2.MORPH_ELLIPSE, (k_w, k_h)) restated on the host: a numpy u8 [k_h, k_w] of 0 / 1 (k_h defaults
+    to k_w).  OpenCV's published rule: r = k_h // 2, c = k_w // 2; row i, with dy = i - r, is empty when |dy| > r and else set on
+    [max(c - dx, 0), min(c + dx + 1, k_w)) for dx = round-half-even(c * sqrt((r^2 - dy^2) / r^2)) in double (r == 0: dx = 0).  Its
+    default anchor is (k_w // 2, k_h // 2).  This reproduces the well-known 3 x 3 element (a cross) and the 5 x 5 one (full but for
+    the four corners of the first and last row, which hold their middle pixel only).  It COULD NOT be compared with OpenCV on any
+    machine of this project (none has it), so larger elements are this formula's, not a recorded cv2 result; a caller that has
+    OpenCV may pass its own element to dilate_u8 / erode_u8."""
+    import math
+    import numpy as np
+    kw = int(k_w)
+    kh = kw if k_h is None else int(k_h)
+    if kw < 1 or kh < 1:
+        raise ValueError(f"ellipse_element: bad size {k_w} x {k_h}")
+    r, c = kh // 2, kw // 2
+    out = np.zeros((kh, kw), np.uint8)
+    for i in range(kh):
+        dy = i - r
+        if abs(dy) <= r:
+            dx = int(round(c * math.sqrt((r * r - dy * dy) / (r * r)))) if r else 0      # round(): half to even, as cvRound
+            out[i, max(c - dx, 0):min(c + dx + 1, kw)] = 1
+    return out
+
+
+def rect_element(k):
+    """cv2.getStructuringElement(cv2.MORPH_RECT, (k, k)) (or (k_w, k_h) for a pair): a numpy u8 array of ones"""
+    import numpy as np
+    kw, kh = (k, k) if isinstance(k, int) else k
+    if int(kw) < 1 or int(kh) < 1:
+        raise ValueError(f"rect_element: bad size {k}")
+    return np.ones((int(kh), int(kw)), np.uint8)
+
+
+_ELEMENTS: Dict[tuple, torch.Tensor] = {}
+_ELEMENTS_MAX = 16                              # the demo uses two elements; a caller that sweeps elements must not pile up device tensors
+
+
+def _element_on(element, device) -> torch.Tensor:
+    """a structuring element (host numpy / torch u8 [kh,kw], or a device tensor) on `device`: one pinned upload per distinct element,
+    the last _ELEMENTS_MAX of them kept"""
+    if torch.is_tensor(element) and element.device.type != "cpu":
+        return element.to(device)
+    import numpy as np
+    e = np.ascontiguousarray(element.numpy() if torch.is_tensor(element) else element)
+    if e.dtype != np.uint8 or e.ndim != 2 or e.size == 0:
+        raise ValueError(f"a structuring element is a uint8 [kh,kw] array, got {e.dtype} {e.shape}")
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:                      # 'cuda' and 'cuda:0' are one device: one entry
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (str(device), e.shape, e.tobytes())
+    if key not in _ELEMENTS:
+        while len(_ELEMENTS) >= _ELEMENTS_MAX:
+            _ELEMENTS.pop(next(iter(_ELEMENTS)))                            # the oldest entry (dicts keep insertion order)
+        _ELEMENTS[key] = upload(torch.from_numpy(e.copy()), device)
+    return _ELEMENTS[key]
+
+
+def _u8_planes(t: torch.Tensor, name: str) -> torch.Tensor:
+    """[H,W] / [N,H,W] / [N,1,H,W] uint8 -> a [N,H,W] view of it (morphology and the brush work on byte maps only)"""
+    if not torch.is_tensor(t) or t.dtype != torch.uint8:
+        raise ValueError(f"{name}: expected a uint8 map, got {getattr(t, 'dtype', type(t).__name__)}")
+    if t.dim() == 2:
+        return t.unsqueeze(0)
+    if t.dim() == 4 and t.shape[1] == 1:
+        return t[:, 0]
+    if t.dim() != 3:
+        raise ValueError(f"{name}: expected [H,W], [N,H,W] or [N,1,H,W], got {tuple(t.shape)}")
+    return t
+
+
+def _morph(mask: torch.Tensor, element, anchor, op: int, name: str) -> torch.Tensor:
+    from . import ops
+    m = _u8_planes(mask, name)
+    elem = _element_on(element, m.device)
+    if anchor is None:
+        anchor = (elem.shape[1] // 2, elem.shape[0] // 2)                 # cv2's Point(-1, -1): the element's centre
+    return ops.morph_u8(m.contiguous(), elem, anchor, op).view(mask.shape)
+
+
+def dilate_u8(mask: torch.Tensor, element, anchor=None) -> torch.Tensor:
+    """cv2.dilate(mask, element, anchor=anchor) with the default border on the device (one launch of mge_morph_u8): mask u8 [H,W],
+    [N,H,W] or [N,1,H,W] of any grey level -> a new map of the same shape.  `element`: a host u8 [kh,kw] array (ellipse_element,
+    rect_element, or OpenCV's own), uploaded once per distinct element, at most 64 x 64; `anchor` (x, y), default the centre."""
+    from . import ops
+    return _morph(mask, element, anchor, ops.MORPH_DILATE, "dilate_u8")
+
+
+def erode_u8(mask: torch.Tensor, element, anchor=None) -> torch.Tensor:
+    """cv2.erode, as dilate_u8 (taps outside the image are left out of the minimum: cv2's default border)."""
+    from . import ops
+    return _morph(mask, element, anchor, ops.MORPH_ERODE, "erode_u8")
+
+
+def brush_segments(segments, n: int, h: int, w: int) -> torch.Tensor:
+    """The host side of brush_u8: `segments` (a list of rows or an integer array [S,8] / [S,7] = sample, x0, y0, x1, y1, thickness,
+    value[, 0]) checked against the ranges of include/michigan_hip/editing/mask_edit.h for an [n,h,w] canvas -> int32 [S,8] on the
+    host.  The C entry point cannot read the device list back, so this is where a bad segment is refused."""
+    import numpy as np
+    from . import ops
+    a = np.asarray(segments if len(segments) else np.zeros((0, 8)), dtype=np.int64)
+    if a.ndim != 2 or a.shape[1] not in (7, 8):
+        raise ValueError(f"brush_u8: segments must be [S,8] = (sample, x0, y0, x1, y1, thickness, value, 0), got {a.shape}")
+    if a.shape[1] == 7:
+        a = np.concatenate([a, np.zeros((a.shape[0], 1), np.int64)], axis=1)
+    if a.shape[0]:
+        bad = ((a[:, 0] < 0) | (a[:, 0] >= n) | (np.abs(a[:, 1:5]) > ops.BRUSH_MAX_COORD).any(axis=1) | (a[:, 5] < 1) |
+               (a[:, 5] > ops.BRUSH_MAX_THICKNESS) | (a[:, 6] < 0) | (a[:, 6] > 255))
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise ValueError("brush_u8: segment %d %s is outside the accepted ranges (0 <= sample < %d, |x|, |y| <= %d, 1 <= thickness <= %d, "
+                             "0 <= value <= 255)" % (i, a[i, :7].tolist(), n, ops.BRUSH_MAX_COORD, ops.BRUSH_MAX_THICKNESS))
+    return torch.from_numpy(a.astype(np.int32))
+
+
+def brush_u8(canvas: torch.Tensor, segments) -> torch.Tensor:
+    """demo.py:431-435 (make_mask: one cv2.line per recorded segment) on the device, IN PLACE: canvas u8 [H,W], [N,H,W] or [N,1,H,W],
+    contiguous; `segments` as brush_segments takes them, applied in order (a pixel keeps the value of the last segment that covers
+    it).  One pinned upload and one launch (mge_brush_u8); no segments, no launch.  The brush is the package's own integer capsule
+    (the header states it), not cv2.line's polygon.  Returns the canvas."""
+    from . import ops
+    m = _u8_planes(canvas, "brush_u8")
+    if not canvas.is_contiguous():
+        raise ValueError("brush_u8: the canvas is painted in place and must be contiguous")
+    segs = brush_segments(segments, *m.shape)
+    ops.brush_u8(m, upload(segs, m.device))
+    return canvas
+
+
+def stroke_hole(mask_stroke: torch.Tensor, ksize: int = 50) -> torch.Tensor:
+    """demo.py:323-324 as one call: cv2.dilate(np.uint8(mask_stroke), getStructuringElement(MORPH_ELLIPSE, (ksize, ksize))) -- the
+    `mask_hole` that stroke_inputs / demo_batch take beside the stroke mask (demo.py:471-472 is ksize=20).  u8 in, u8 out."""
+    return dilate_u8(mask_stroke, ellipse_element(ksize))
 
 
 def _decoded(t, name: str, channels: int, n: Optional[int] = None) -> torch.Tensor:
@@ -501,7 +637,8 @@ class DeviceInputPipeline:
     def demo_batch(self, *, label_ref, label_tag, mask_orient, orient_ref, image_ref, image_tag, mask_stroke=None,
                    mask_hole=None) -> Dict[str, torch.Tensor]:
         """demo_inference_dataLoad (base_dataset.py:162-276); the keys it returns, except `path`.  Its `orient_stroke` argument
-        (demo.py:325-326) is derived here from mask_stroke; mask_hole, the dilated stroke (demo.py:323-324), stays the caller's."""
+        (demo.py:325-326) is derived here from mask_stroke; mask_hole, the dilated stroke (demo.py:323-324), is `stroke_hole(mask_stroke)`
+        and stays an argument: the two are given together or not at all (michigan_amd.demo.EditSession passes both)."""
         opt, dev = self.opt, self.device
         self._check_options("demo_batch")
         if getattr(opt, "expand_tag_mask", False):

@@ -2329,6 +2329,55 @@ def stroke_orient(stroke: torch.Tensor, want_idx: bool = False, want_conf: bool 
     return (rgb,) + extra if extra else rgb
 
 
+BRUSH_MAX_THICKNESS, BRUSH_MAX_COORD, MORPH_MAX_K = 255, 8191, 64          # include/michigan_hip/editing/mask_edit.h
+MORPH_DILATE, MORPH_ERODE = 0, 1
+
+
+def brush_u8(canvas: torch.Tensor, segs: torch.Tensor) -> torch.Tensor:
+    """demo.py:431-435 (make_mask) in one launch (mge_brush_u8): canvas u8 [N,H,W], contiguous, painted IN PLACE and returned; segs int32
+    [S,8] on the canvas' device = (sample, x0, y0, x1, y1, thickness, value, 0), applied in order with the integer capsule rule of
+    include/michigan_hip/editing/mask_edit.h (the package's own brush, not cv2.line's polygon).  CALLER'S OBLIGATION: every row
+    of `segs` is inside the header's ranges (0 <= sample < N, |x|, |y| <= 8191, 1 <= thickness <= 255, 0 <= value <= 255).  Nothing
+    here reads the device list back, so a row outside them does NOT raise: the kernel skips it silently.  inputs.brush_u8 checks the
+    list while it is still on the host and raises; call this directly only with a list that went through inputs.brush_segments.
+    S == 0 launches nothing."""
+    if canvas.dim() != 3 or canvas.dtype != torch.uint8 or not canvas.is_contiguous():
+        raise ValueError(f"brush_u8: canvas must be a contiguous uint8 [N,H,W], got {canvas.dtype} {tuple(canvas.shape)}")
+    if segs.dim() != 2 or segs.shape[1] != 8 or segs.dtype != torch.int32 or segs.device != canvas.device:
+        raise ValueError(f"brush_u8: segs must be int32 [S,8] on {canvas.device}, got {segs.dtype} {tuple(segs.shape)} on {segs.device}")
+    n, h, w = canvas.shape
+    if n < 1 or not (1 <= h <= BRUSH_MAX_COORD + 1 and 1 <= w <= BRUSH_MAX_COORD + 1) or n * h * w >= 1 << 31:
+        raise ValueError(f"brush_u8: bad geometry {tuple(canvas.shape)} (H, W in [1, {BRUSH_MAX_COORD + 1}], N H W < 2^31)")
+    segs = segs.contiguous()
+    C.backend().mge_brush_u8(_p(canvas), _p(segs), segs.shape[0], n, h, w, _stream(canvas))
+    return canvas
+
+
+def morph_u8(src: torch.Tensor, elem: torch.Tensor, anchor, op: int) -> torch.Tensor:
+    """cv2.dilate (op MORPH_DILATE) / cv2.erode (op MORPH_ERODE) with their default border in one launch (mge_morph_u8): src u8
+    [N,H,W] of any grey level, elem u8 [kh,kw] on the same device (non-zero = tap, any shape of element up to 64 x 64), anchor
+    (ax, ay) inside it, cv2's (x, y) order -> a new u8 [N,H,W]."""
+    if src.dim() != 3 or src.dtype != torch.uint8:
+        raise ValueError(f"morph_u8: src must be uint8 [N,H,W], got {src.dtype} {tuple(src.shape)}")
+    if elem.dim() != 2 or elem.dtype != torch.uint8 or elem.device != src.device:
+        raise ValueError(f"morph_u8: elem must be uint8 [kh,kw] on {src.device}, got {elem.dtype} {tuple(elem.shape)} on {elem.device}")
+    n, h, w = src.shape
+    kh, kw = elem.shape
+    ax, ay = (int(v) for v in anchor)
+    if not (1 <= kh <= MORPH_MAX_K and 1 <= kw <= MORPH_MAX_K):
+        raise ValueError(f"morph_u8: the element is {kh} x {kw}, at most {MORPH_MAX_K} x {MORPH_MAX_K} is supported")
+    if not (0 <= ay < kh and 0 <= ax < kw):
+        raise ValueError(f"morph_u8: anchor (x {ax}, y {ay}) outside the {kh} x {kw} element")
+    if op not in (MORPH_DILATE, MORPH_ERODE):
+        raise ValueError(f"morph_u8: op must be MORPH_DILATE or MORPH_ERODE, got {op}")
+    if n < 1 or h < 1 or w < 1 or n * h * w >= 1 << 31:
+        raise ValueError(f"morph_u8: bad geometry {tuple(src.shape)} (N H W must be in [1, 2^31))")
+    src, elem = src.contiguous(), elem.contiguous()
+    dst = torch.empty((n, h, w), dtype=torch.uint8, device=src.device)
+    C.backend().mge_morph_u8(_p(src), _p(elem), kh, kw, ay, ax, op, _p(dst), n, h, w, _stream(src))
+    return dst
+
+
 def interp_nearest_table(src: int, dst: int, device=None) -> Optional[torch.Tensor]:
     """int32 [dst]: the source index F.interpolate(mode='nearest') reads for each of `dst` outputs of a `src`-long axis -- taken from
     F.interpolate itself on an arange, so it is that function's rule by construction.  None = identity (src == dst)."""
