@@ -202,9 +202,18 @@ _EDIT_PROTOS = {
     "mge_brush_u8": ([_vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
     "mge_morph_u8": ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp], _i32),
 }
+# include/michigan_hip/evaluation/quality.h: the quality extension group (prefix mgq_), bound like the editing group: a table of its
+# own, outside the versioned table.  The window of mgq_image_quality_u8 is a HOST array of doubles.
+_QUALITY_PROTOS = {
+    "mgq_quality_workspace": ([_i32, _i32, _i32, _i32], _i64),
+    "mgq_image_quality_u8": ([_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
+    "mgq_orient_distance_u8": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp], _i32),
+}
+_EXTENSION_PROTOS = dict(_EDIT_PROTOS, **_QUALITY_PROTOS)
 EXPORTED_SYMBOLS = tuple(_PROTOS)              # the whole ABI: tests/test_cabi_host.py holds it to the headers and to the library's exports
 _NO_STATUS = {"mg_wgrad_det_workspace", "mg_norm_apply2_supported", "mg_grad_slot_blocks", "mg_pack_job_blocks", "mg_sn_layer_blocks", "mg_stats_workspace", "mg_sizeof_desc", "mg_abi_version", "mg_last_error", "mg_noise_field_len", "mg_bicubic_ksize",
               "mg_feat_moment_workspace"}
+_EXTENSION_NO_STATUS = {"mgq_quality_workspace"}               # the same for the extension groups: a byte count, not a status
 # entry points that take their descriptor by reference: the first argument is a pointer to one of the Structure mirrors above
 _BY_REF = {fn for fn, (argtypes, _) in _PROTOS.items()
            if argtypes and isinstance(getattr(argtypes[0], "_type_", None), type) and issubclass(argtypes[0]._type_, ctypes.Structure)}
@@ -234,7 +243,7 @@ class HipBackend:
         # torch must already have loaded its libamdhip64 so that we bind to the same runtime.
         import torch  # noqa: F401
         self._lib = ctypes.CDLL(path)
-        for fn, (argtypes, restype) in list(_PROTOS.items()) + list(_EDIT_PROTOS.items()):
+        for fn, (argtypes, restype) in list(_PROTOS.items()) + list(_EXTENSION_PROTOS.items()):
             f = getattr(self._lib, fn)          # AttributeError if a symbol is missing
             f.argtypes, f.restype = argtypes, restype
         if self._lib.mg_abi_version() != MG_ABI_VERSION:
@@ -243,10 +252,10 @@ class HipBackend:
             raise RuntimeError("ctypes mirror of the descriptor structs is out of sync with include/michigan_hip.h")
 
     def __getattr__(self, fn):
-        if fn not in _PROTOS and fn not in _EDIT_PROTOS:
+        if fn not in _PROTOS and fn not in _EXTENSION_PROTOS:
             raise AttributeError(fn)
         raw = getattr(self._lib, fn)
-        if fn in _NO_STATUS:
+        if fn in _NO_STATUS or fn in _EXTENSION_NO_STATUS:
             return raw
         by_ref = fn in _BY_REF
 

@@ -20,7 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from .inputs import DeviceInputPipeline
+from .inputs import DeviceInputPipeline, _pad_zeros
 
 
 def tensor2im(image: torch.Tensor) -> torch.Tensor:
@@ -66,33 +66,54 @@ def _stacked(opt, triples) -> dict:
     return out
 
 
-def generate(opt, model, names: Sequence[Tuple[str, str, str]], rng: Optional[_random.Random] = None,
-             generator: Optional[torch.Generator] = None) -> torch.Tensor:
-    """inference.py:33-48 for the (ref, tag, orient) name triples `names`: uint8 [len(names), crop, crop, 3] on the model's device.
-    The triples run in batches of up to opt.batchSize; a batch holds triples of one hole rule (orient == tag or not,
-    base_dataset.py:116) and of one stored size."""
+def generated_batches(opt, model, names: Sequence[Tuple[str, str, str]], rng: Optional[_random.Random] = None,
+                      generator: Optional[torch.Generator] = None, given_orientation: bool = False):
+    """The batch loop of `generate`, as a generator: yields (data, generated fp32 [n,3,H,W]) per batch -- the loader's dict and the
+    net's output, remove_background applied, before tensor2im and before the add_th border comes off.  The triples run in batches of
+    up to opt.batchSize; a batch holds triples of one hole rule (orient == tag or not, base_dataset.py:116) and of one stored size.
+    `data["names"]` lists the batch's triples.  given_orientation (michigan_amd.evaluate): two more maps cut at the batch's own window,
+    `orient_given` (the orientation sample's map, uint8 values as fp32 [n,1,H,W]) and `orient_given_mask` (label_tag AND the
+    orientation sample's label)."""
     device = next(model.parameters()).device
     pipe = DeviceInputPipeline(opt, device, rng=rng, generator=generator)
     bs = max(1, int(getattr(opt, "batchSize", 1)))
     names = [tuple(t) for t in names]
-    out, i = [], 0
+    i = 0
     while i < len(names):
         same = names[i][2] == names[i][1]
         j = i + 1
         while j < len(names) and j - i < bs and (names[j][2] == names[j][1]) == same:
             j += 1
-        data = pipe.inference_batch(same_orient=same, **_stacked(opt, names[i:j]))
+        files = _stacked(opt, names[i:j])
+        data = pipe.inference_batch(same_orient=same, **files)
+        if given_orientation:                                                     # after the batch: its draws and launches are untouched
+            crop = pipe.last_window.to(device)
+            pad = (lambda t: _pad_zeros(t, int(opt.add_th))) if getattr(opt, "add_zeros", False) else (lambda t: t)
+            data["orient_given"] = pipe._map(pad(files["orient_ref"]), crop, mode=1)
+            data["orient_given_mask"] = pipe._map(pad(files["orient_mask"]), crop, mode=1, unknown_label=int(opt.label_nc), mul=data["label_tag"])
+        data["names"] = names[i:j]
         generated = model(data, "inference").float()
         if getattr(opt, "remove_background", False):                              # inference.py:41-42
             label = data["label_tag"].float()
             generated = generated * label + data["image_tag"] * (1 - label)
-        image = tensor2im(generated)
-        if getattr(opt, "add_feat_zeros", False) or getattr(opt, "add_zeros", False):       # :44-48: the add_th border comes off
-            o, c = int(opt.add_th / 2), int(opt.crop_size)
-            image = image[:, o:o + c, o:o + c, :]
-        out.append(image.contiguous())
+        yield data, generated
         i = j
-    return torch.cat(out)
+
+
+def crop_border(opt, image: torch.Tensor) -> torch.Tensor:
+    """inference.py:44-48 for a [N,H,W,C] batch: the add_th border comes off under add_feat_zeros / add_zeros"""
+    if getattr(opt, "add_feat_zeros", False) or getattr(opt, "add_zeros", False):
+        o, c = int(opt.add_th / 2), int(opt.crop_size)
+        image = image[:, o:o + c, o:o + c, :]
+    return image
+
+
+def generate(opt, model, names: Sequence[Tuple[str, str, str]], rng: Optional[_random.Random] = None,
+             generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """inference.py:33-48 for the (ref, tag, orient) name triples `names`: uint8 [len(names), crop, crop, 3] on the model's device
+    (the batches of `generated_batches`, through tensor2im)."""
+    return torch.cat([crop_border(opt, tensor2im(generated)).contiguous()
+                      for _, generated in generated_batches(opt, model, names, rng=rng, generator=generator)])
 
 
 def build_model(opt):
@@ -106,8 +127,8 @@ def build_model(opt):
     return model.eval()
 
 
-def parse(argv: Optional[List[str]] = None):
-    from .train import build_parser, finish_options
+def build_inference_parser():
+    from .train import build_parser
     p = build_parser(is_train=False)
     p.add_argument("--inference_ref_name", type=str, default="57541", help="which reference sample")
     p.add_argument("--inference_tag_name", type=str, default="56001", help="which target sample")
@@ -119,7 +140,12 @@ def parse(argv: Optional[List[str]] = None):
     p.add_argument("--expand_tag_mask", action="store_true", help="refused: a 25 x 25 cv2.dilate of the target mask")
     p.add_argument("--pairs_file", type=str, default="", help="lines `ref tag orient`: one <tag>_from_<ref>.png each")
     p.set_defaults(batchSize=1, no_flip=True, serial_batches=True)
-    return finish_options(p.parse_args(argv), is_train=False)
+    return p
+
+
+def parse(argv: Optional[List[str]] = None):
+    from .train import finish_options
+    return finish_options(build_inference_parser().parse_args(argv), is_train=False)
 
 
 def main(argv: Optional[List[str]] = None) -> int:

@@ -498,6 +498,7 @@ class DeviceInputPipeline:
         crop_h = self.draw_params(n)
         if int(crop_h[:, :2].min()) < 0 or int(crop_h[:, :2].max()) + self.crop_size > self.load_size:
             raise ValueError("crop window outside the load_size x load_size source")
+        self.last_window = crop_h                                               # for a caller that cuts further maps at the same window (michigan_amd.evaluate)
         return crop_h
 
     def _resized(self, image: torch.Tensor) -> torch.Tensor:

@@ -2378,6 +2378,62 @@ def morph_u8(src: torch.Tensor, elem: torch.Tensor, anchor, op: int) -> torch.Te
     return dst
 
 
+QUALITY_TILE, QUALITY_MIN_K, QUALITY_MAX_K, QUALITY_MAX_C, QUALITY_WS_SLOTS = 16, 3, 15, 4, 6          # include/michigan_hip/evaluation/quality.h
+QUALITY_INT_TERMS, QUALITY_SSIM_TERMS, ORIENT_PERIOD = 4, 2, 255
+
+
+def image_quality_u8(a: torch.Tensor, b: torch.Tensor, mask: Optional[torch.Tensor], window) -> Tuple[torch.Tensor, torch.Tensor]:
+    """PSNR / SSIM ingredients of two image batches in one pass (mgq_image_quality_u8, two launches): a, b u8 [N,H,W,C] NHWC, 1 <= C
+    <= 4, mask u8 [N,H,W] or None (non-zero = in), window a HOST float64 array of k taps (k odd, 3 <= k <= 15, H, W >= k) ->
+    (int64 [N,C,4] = sse, sse under the mask, mask count, valid-region mask count; float64 [N,C,2] = ssim sum over the valid region,
+    the same under the mask), as include/michigan_hip/evaluation/quality.h defines them.  Views are made dense here; anything else
+    raises ValueError before a call."""
+    import numpy as np
+    if a.dim() != 4 or b.shape != a.shape or a.dtype != torch.uint8 or b.dtype != torch.uint8 or b.device != a.device:
+        raise ValueError(f"image_quality_u8: a and b must be uint8 [N,H,W,C] of one shape on one device, got {a.dtype} {tuple(a.shape)} and {b.dtype} {tuple(b.shape)}")
+    n, h, w, c = a.shape
+    if not 1 <= c <= QUALITY_MAX_C:
+        raise ValueError(f"image_quality_u8: {c} channels (NHWC with 1 <= C <= {QUALITY_MAX_C}); got {tuple(a.shape)}")
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (n, h, w) or mask.device != a.device):
+        raise ValueError(f"image_quality_u8: mask must be uint8 {(n, h, w)} on {a.device}, got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
+    win = np.ascontiguousarray(np.asarray(window, dtype=np.float64))
+    k = win.size
+    if win.ndim != 1 or k % 2 == 0 or not QUALITY_MIN_K <= k <= QUALITY_MAX_K:
+        raise ValueError(f"image_quality_u8: the window must be a vector of k taps, k odd in [{QUALITY_MIN_K}, {QUALITY_MAX_K}], got shape {win.shape}")
+    if not np.isfinite(win).all():
+        raise ValueError("image_quality_u8: the window holds a non-finite tap")
+    if h < k or w < k:
+        raise ValueError(f"image_quality_u8: the image {h} x {w} is smaller than the window k={k}")
+    if n < 1 or n * h * w * c >= 1 << 31:
+        raise ValueError(f"image_quality_u8: bad geometry {tuple(a.shape)} (N H W C must be in [1, 2^31))")
+    a, b = a.contiguous(), b.contiguous()
+    mask = None if mask is None else mask.contiguous()
+    be = C.backend()
+    ws = torch.empty(be.mgq_quality_workspace(n, h, w, c) // 8, dtype=torch.int64, device=a.device)
+    out_int = torch.empty((n, c, QUALITY_INT_TERMS), dtype=torch.int64, device=a.device)
+    out_ssim = torch.empty((n, c, QUALITY_SSIM_TERMS), dtype=torch.float64, device=a.device)
+    be.mgq_image_quality_u8(_p(a), _p(b), _p(mask), ctypes.c_void_p(win.ctypes.data), k, _p(ws), _p(out_int), _p(out_ssim), n, h, w, c, _stream(a))
+    return out_int, out_ssim
+
+
+def orient_distance_u8(a: torch.Tensor, b: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """Agreement of two orientation maps (mgq_orient_distance_u8): a, b, mask u8 [N,H,W] -> int64 [N,2] = (sum over the pixels with
+    mask != 0 of min(|a - b|, 255 - |a - b|), their count).  The coding has period 255."""
+    if a.dim() != 3 or a.dtype != torch.uint8:
+        raise ValueError(f"orient_distance_u8: a must be uint8 [N,H,W], got {a.dtype} {tuple(a.shape)}")
+    for name, t in (("b", b), ("mask", mask)):
+        if t is None or t.dtype != torch.uint8 or t.shape != a.shape or t.device != a.device:
+            raise ValueError(f"orient_distance_u8: {name} must be uint8 {tuple(a.shape)} on {a.device}, got "
+                             + ("None" if t is None else f"{t.dtype} {tuple(t.shape)} on {t.device}"))
+    n, h, w = a.shape
+    if n < 1 or h < 1 or w < 1 or n * h * w >= 1 << 31:
+        raise ValueError(f"orient_distance_u8: bad geometry {tuple(a.shape)} (N H W must be in [1, 2^31))")
+    a, b, mask = a.contiguous(), b.contiguous(), mask.contiguous()
+    out = torch.empty((n, 2), dtype=torch.int64, device=a.device)
+    C.backend().mgq_orient_distance_u8(_p(a), _p(b), _p(mask), _p(out), n, h, w, _stream(a))
+    return out
+
+
 def interp_nearest_table(src: int, dst: int, device=None) -> Optional[torch.Tensor]:
     """int32 [dst]: the source index F.interpolate(mode='nearest') reads for each of `dst` outputs of a `src`-long axis -- taken from
     F.interpolate itself on an arange, so it is that function's rule by construction.  None = identity (src == dst)."""

@@ -94,6 +94,9 @@ def build_parser(is_train: bool = True) -> argparse.ArgumentParser:
         p.add_argument("--D_steps_per_G", type=int, default=1)
         p.add_argument("--G_steps_per_D", type=int, default=1)
         p.add_argument("--no_discriminator", action="store_true")
+        p.add_argument("--val_freq", type=int, default=0, help="0 = off; else every N-th epoch rank 0 measures the generator on "
+                       "<data_dir>/val_* (michigan_amd.evaluate, protocol reconstruct) and appends the pooled line to val_log.txt")
+        p.add_argument("--val_max_samples", type=int, default=64, help="how many val_* samples a validation pass takes (0 = all)")
     return p
 
 
@@ -276,10 +279,49 @@ def train(opt, loaders=None) -> dict:
                 print("saving the model at the end of epoch %d, iters %d" % (epoch, iter_counter.total_steps_so_far))
             trainer.save("latest")
             trainer.save(epoch)
+        if getattr(opt, "val_freq", 0) > 0 and epoch % opt.val_freq == 0 and rank == 0:
+            validate(opt, trainer.pix2pix_model_on_one_gpu, epoch, os.path.join(run_dir, "val_log.txt"))
     done["losses"] = _floats(trainer.get_latest_losses())
     if rank == 0:
         print("Training was successfully finished.")
     return done
+
+
+def validate(opt, model, epoch: int, log_name: str) -> dict:
+    """--val_freq: evaluate.evaluate(protocol 'reconstruct') over <data_dir>/val_*, capped by --val_max_samples, on `model` in eval();
+    the pooled values go to `log_name` as one line and every module goes back to the mode it was in.  Nothing of the training run moves:
+    the pass has a random.Random and a torch.Generator of its own (seeded by --seed and the epoch), runs under no_grad with the global
+    torch generators forked, in eval() no spectral-norm vector and no running statistic is written, and the job-shared host generator
+    (the encoder draws its mask expansion from it while opt.isTrain, in eval() too) is seeded for the pass and put back afterwards.
+    The files are cut deterministically: load_size = crop_size, no flip."""
+    import copy
+    from . import evaluate as E
+    dev = next(model.parameters()).device
+    vopt = copy.copy(opt)
+    vopt.subset, vopt.no_flip, vopt.load_size, vopt.add_zeros = "val", True, opt.crop_size, False
+    vopt.batchSize = max(1, opt.batchSize // parallel.world_size())
+    seed = (opt.seed if opt.seed is not None else 0) + 7919 * epoch
+    generator = torch.Generator(device=dev)
+    generator.manual_seed(seed)
+    names = E.reconstruct_names(vopt, getattr(opt, "val_max_samples", 0))
+    modes = [(m, m.training) for m in model.modules()]              # the frozen nets are in eval() inside a model that trains
+    shared = parallel.shared_rng()
+    shared_state = shared.getstate()
+    model.eval()
+    try:
+        shared.seed(seed)
+        with torch.no_grad(), torch.random.fork_rng(devices=[dev] if dev.type == "cuda" else []):
+            result = E.evaluate(vopt, model, names, "reconstruct", rng=_random.Random(seed), generator=generator)
+    finally:
+        shared.setstate(shared_state)
+        for m, mode in modes:
+            m.training = mode
+    message = "(epoch: %d, samples: %d) " % (epoch, result["samples"]) + "".join(
+        "%s: %.4f " % (k, result["pooled"][k]) for k in E.POOLED_KEYS[1:])
+    print("validation " + message)
+    with open(log_name, "a") as f:
+        f.write("%s\n" % message)
+    return result
 
 
 def save_generated(trainer, path: str):
