@@ -209,7 +209,13 @@ _QUALITY_PROTOS = {
     "mgq_image_quality_u8": ([_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
     "mgq_orient_distance_u8": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp], _i32),
 }
-_EXTENSION_PROTOS = dict(_EDIT_PROTOS, **_QUALITY_PROTOS)
+# include/michigan_hip/losses/orient_dog.h: the loss extension group (prefix mgl_), bound like the other two: the tail of the
+# orientation loss under the difference-of-Gaussians bank.  (conf_raw, idx, label, label_ch, label_nstride, hair, hair_nstride, ...)
+_LOSS_PROTOS = {
+    "mgl_orient_dog_fwd": ([_vp, _vp, _vp, _i32, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _vp], _i32),
+    "mgl_orient_dog_bwd": ([_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp], _i32),
+}
+_EXTENSION_PROTOS = dict(_EDIT_PROTOS, **_QUALITY_PROTOS, **_LOSS_PROTOS)
 EXPORTED_SYMBOLS = tuple(_PROTOS)              # the whole ABI: tests/test_cabi_host.py holds it to the headers and to the library's exports
 _NO_STATUS = {"mg_wgrad_det_workspace", "mg_norm_apply2_supported", "mg_grad_slot_blocks", "mg_pack_job_blocks", "mg_sn_layer_blocks", "mg_stats_workspace", "mg_sizeof_desc", "mg_abi_version", "mg_last_error", "mg_noise_field_len", "mg_bicubic_ksize",
               "mg_feat_moment_workspace"}

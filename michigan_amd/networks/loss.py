@@ -2,7 +2,7 @@
 
 Reductions run in fp32 on whatever dtype the discriminator / VGG towers produced, as fused HIP launches: the hinge GAN
 loss with its wide-edge weight mask (mg_hinge_*, mg_wide_edge_weight), discriminator feature matching and the VGG taps
-(mg_l1_mean_*), the Gabor orientation loss (mg_gabor_argmax_*), and the image-space Lab colour / background / RGB L1
+(mg_l1_mean_*), the orientation loss under either filter bank (mg_gabor_argmax_*, then mg_orient_loss_* / mgl_orient_dog_*), and the image-space Lab colour / background / RGB L1
 terms as one pass (mg_color_loss_*), the unpaired stage's hair-average Lab term (mg_hair_lab_*, fused with the background
 term in the model), and the style / content terms as fused feature-moment passes over the VGG taps (mg_feat_moment_loss_*).  The
 balance_Lab weighting is out of scope; under michigan_amd.dropin style / content stay the reference's own class."""
@@ -178,29 +178,37 @@ class VGGLoss(nn.Module):
 
 
 class L1OLoss(nn.Module):
-    """Orientation loss (reference: loss.py:274-385, 'gabor' filter): the dominant orientation of the generated
-    image -- arg-max over 32 oriented Gabor responses of its gray version, weighted by a tanh confidence --
-    must match the orientation label inside the hair mask.  The filter bank, clamp, max and arg-max are one HIP
-    launch (ops.gabor_argmax); what remains here are a few passes over single-channel [N,H,W] maps."""
+    """Orientation loss (reference: loss.py:274-385): the dominant orientation of the generated image -- arg-max over 32 oriented
+    filter responses of its gray version, weighted by a confidence -- must match the orientation label inside the hair mask.  The mode
+    rule is the reference's: 'gabor' in opt.orient_filter selects the Gabor bank with a tanh confidence, anything else the
+    difference-of-Gaussians bank that made the dataset's labels, whose confidence is the masked response divided by its maximum over the
+    whole batch (one process per GPU: the rank's own maximum, like a DataParallel replica of the reference).  The filter bank, clamp,
+    max and arg-max are one HIP launch (ops.gabor_argmax, any 32 x 17 x 17 bank); everything behind it is one fused reduction per mode."""
 
     def __init__(self, opt, channel_in=1, channel_out=1, stride=1, padding=8):
         super().__init__()
-        if getattr(opt, "orient_filter", "gabor") != "gabor":
-            raise NotImplementedError("orientation loss: only the (default) Gabor filter bank is implemented")
         self.opt = opt
+        self.mode = getattr(opt, "orient_filter", "gabor")
         self.numKernels, self.kernel_size = 32, 17
-        self.register_buffer("bank", ops.gabor_bank(), persistent=False)
+        self.register_buffer("bank", ops.gabor_bank() if "gabor" in self.mode else ops.dog_bank(), persistent=False)
 
     def forward(self, fake_image0, orientation_label0, input_semantics):
         img = fake_image0.permute(0, 2, 3, 1)                       # zero-copy for the generator's NHWC output
         conf_raw, idx = ops.gabor_argmax(img, self.bank.to(img.device))
-        # everything behind the arg-max -- tanh confidence, (sin 2a, cos 2a) of the winning filter, the masked L1 against the label,
-        # the confidence term -- is one fused reduction (mg_orient_loss_*): ~45 launches of single-channel maps per step before
+        gabor = "gabor" in self.mode
+        # everything behind the arg-max -- the confidence, (sin 2a, cos 2a) of the winning filter, the masked L1 against the label,
+        # the confidence term -- is one fused reduction (mg_orient_loss_* / mgl_orient_dog_*): ~45 launches of single-channel maps per step before
         if (not self.opt.use_ig) == (orientation_label0.shape[1] == 1) and orientation_label0.shape[1] in (1, 2):
-            orient_loss, confidence_loss = ops.orient_loss(conf_raw, idx, orientation_label0, input_semantics.detach()[:, 1])
+            tail = ops.orient_loss if gabor else ops.orient_loss_dog
+            orient_loss, confidence_loss = tail(conf_raw, idx, orientation_label0, input_semantics.detach()[:, 1])
             return orient_loss, confidence_loss
-        confidence = ((torch.tanh(conf_raw) + 1) / 2.0).unsqueeze(1)
         hair = input_semantics[:, 1:2].float()
+        if gabor:
+            confidence = ((torch.tanh(conf_raw) + 1) / 2.0).unsqueeze(1)
+        else:
+            confidence = conf_raw.unsqueeze(1) * hair
+            confidence = confidence / torch.max(confidence)
+            confidence = confidence * (~(confidence <= 0)).float()
         ang = (idx.float() * (math.pi / self.numKernels)).unsqueeze(1)
         orient_fake = torch.cat([torch.sin(2 * ang), torch.cos(2 * ang)], dim=1) * confidence
         if not self.opt.use_ig:
@@ -209,8 +217,11 @@ class L1OLoss(nn.Module):
         else:
             orient_label = orientation_label0.float()
         orient_loss = F.l1_loss(orient_fake * hair, (orient_label * hair).detach())
-        conf = torch.clamp(confidence, 0.001, 1)
-        confidence_loss = -torch.sum(torch.log(conf) * hair) / torch.sum(hair)
+        if gabor:
+            conf = torch.clamp(confidence, 0.001, 1)
+            confidence_loss = -torch.sum(torch.log(conf) * hair) / torch.sum(hair)
+        else:
+            confidence_loss = torch.sum(torch.abs(confidence * hair - hair.detach())) / (torch.sum(hair) + 1e-5)
         return orient_loss, confidence_loss
 
 

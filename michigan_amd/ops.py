@@ -1848,6 +1848,53 @@ def orient_loss(conf_raw: torch.Tensor, idx: torch.Tensor, label: torch.Tensor, 
     return _OrientLossFn.apply(conf_raw.contiguous(), idx.contiguous(), label, hair)
 
 
+ORIENT_DOG_BLOCKS, ORIENT_DOG_WS_ROWS, ORIENT_DOG_OUT = 1024, 7, 8       # MGL_ORIENT_DOG_* (include/michigan_hip/losses/orient_dog.h)
+
+
+class _OrientDogLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, conf_raw, idx, label, hair):
+        n, h, w = conf_raw.shape
+        out = torch.empty(ORIENT_DOG_OUT, dtype=torch.float32, device=conf_raw.device)
+        ws = torch.empty(ORIENT_DOG_WS_ROWS * ORIENT_DOG_BLOCKS, dtype=torch.float32, device=conf_raw.device)
+        hp, hs = _plane_args(hair)
+        C.backend().mgl_orient_dog_fwd(_p(conf_raw), _p(idx), _p(label), label.shape[1], label.stride(0), hp, hs, n, h * w, _p(out), _p(ws),
+                                       _stream(conf_raw))
+        ctx.save_for_backward(conf_raw, idx, label, hair, out)
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_orient, g_conf):
+        conf_raw, idx, label, hair, out = ctx.saved_tensors
+        if g_orient is None and g_conf is None:
+            return None, None, None, None
+        n, h, w = conf_raw.shape
+        fix = lambda g: None if g is None else (g if g.dtype == torch.float32 else g.float())
+        g_orient, g_conf = fix(g_orient), fix(g_conf)
+        hp, hs = _plane_args(hair)
+        d = torch.empty_like(conf_raw)
+        C.backend().mgl_orient_dog_bwd(_p(conf_raw), _p(idx), _p(label), label.shape[1], label.stride(0), hp, hs, _p(g_orient), _p(g_conf),
+                                       _p(out), n, h * w, _p(d), _stream(conf_raw))
+        return d, None, None, None
+
+
+def orient_loss_dog(conf_raw: torch.Tensor, idx: torch.Tensor, label: torch.Tensor, hair: torch.Tensor):
+    """(orientation L1, confidence loss) of L1OLoss behind the arg-max under the difference-of-Gaussians bank (loss.py:320-349 and the
+    DoG branch of 352-385): conf_raw fp32 [N,H,W], idx u8 [N,H,W], label fp32 [N, 1 or 2, H, W] (0..255 angle map or (sin 2t, cos 2t)
+    planes), hair fp32 [N, H, W] view.  The confidence is conf_raw * hair divided by its maximum over the WHOLE tensor -- across the
+    samples of the batch; with no positive response under the hair anywhere both losses are NaN, as in the reference.  Under one process
+    per GPU that maximum is the rank's own, which is what a replica of the reference's DataParallel computes: no collective is needed.
+    Three launches forward, one backward, no read-back."""
+    label = label.detach().float()
+    if not label.is_contiguous():
+        label = label.contiguous()
+    hair = hair.detach()
+    if hair.dtype != torch.float32:
+        hair = hair.float()
+    return _OrientDogLossFn.apply(conf_raw.contiguous(), idx.contiguous(), label, hair)
+
+
 COLOR_LAB, COLOR_RGB, COLOR_BACKGROUND = 1, 2, 4      # `flags` bits of mg_color_loss_*
 
 
