@@ -362,9 +362,7 @@ def drop_arena_pack_table(arena):
 
 
 def _pack_weight(w0, w1, dtype, rows_p, cols_p, mode):
-    w0 = w0.detach().float().contiguous()
-    if w1 is not None:
-        w1 = w1.detach().float().contiguous()
+    w0, w1 = _f32_dense(w0), _f32_dense(w1)
     cout, cin, kh, kw = w0.shape
     dst = torch.empty((kh * kw, rows_p, cols_p), dtype=dtype, device=w0.device)
     C.backend().mg_pack_weight(_p(w0), _p(w1), _p(dst), _dtype_code(dtype),
@@ -769,27 +767,35 @@ def act_backward(dy: torch.Tensor, y: torch.Tensor, act: int, slope: float) -> t
 # ----------------------------------------------------------------------------
 # conv2d
 # ----------------------------------------------------------------------------
+def _conv_forward(who, x, weight, bias, resid, stride, pad, dilation, act, slope, **launch):
+    """The forward launch of `who` (conv2d / conv2d_infer, for the error text) on a dense NHWC `x` whose channels cover the weight's:
+    output geometry, packed weight, fp32 bias, output, residual check.  `launch`: what only one of them passes to _launch_conv."""
+    n, h, w, cx = x.shape
+    cout, cin, kh, kw = weight.shape
+    ho = (h + 2 * pad - dilation * (kh - 1) - 1) // stride + 1
+    wo = (w + 2 * pad - dilation * (kw - 1) - 1) // stride + 1
+    wp = pack_weight(weight, None, x.dtype, _roundup(cout, 128), cx, 0)
+    bp = _f32_dense(bias)
+    out = torch.empty((n, ho, wo, cout), dtype=x.dtype, device=x.device)
+    if resid is not None:
+        resid = _nhwc(resid)
+        if resid.shape != out.shape or resid.dtype != out.dtype:
+            raise ValueError(f"{who}: residual must match the output")
+    _launch_conv(x, wp, out, bp, fwd_taps(kh, kw, pad, dilation), Hj=ho, Wj=wo, isy=stride, isx=stride,
+                 cout=cout, cout_gemm=cout, act=act, slope=slope, resid=resid, **launch)
+    return out
+
+
 class _Conv2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, resid, stride, pad, act, slope, x_relu=False, sink=None, x_mask_slope=0.0):
         ctx.sink = sink
         ctx.x_mask_slope = float(x_mask_slope)
         x = _nhwc(x)
-        n, h, w, cx = x.shape
-        cout, cin, kh, kw = weight.shape
+        cx, cin = x.shape[3], weight.shape[1]
         if cx < cin or cx % 8:
             raise ValueError(f"conv2d: input has {cx} channels, weight expects {cin} (input must be >= and a multiple of 8)")
-        ho = (h + 2 * pad - kh) // stride + 1
-        wo = (w + 2 * pad - kw) // stride + 1
-        wp = pack_weight(weight, None, x.dtype, _roundup(cout, 128), cx, 0)
-        bp = bias.detach().float().contiguous() if bias is not None else None
-        out = torch.empty((n, ho, wo, cout), dtype=x.dtype, device=x.device)
-        if resid is not None:
-            resid = _nhwc(resid)
-            if resid.shape != out.shape or resid.dtype != out.dtype:
-                raise ValueError("conv2d: residual must match the output")
-        _launch_conv(x, wp, out, bp, fwd_taps(kh, kw, pad), Hj=ho, Wj=wo, isy=stride, isx=stride,
-                     cout=cout, cout_gemm=cout, act=act, slope=slope, resid=resid, algo_cin=cin)
+        out = _conv_forward("conv2d", x, weight, bias, resid, stride, pad, 1, act, slope, algo_cin=cin)
         ctx.save_for_backward(x, weight, out if act != ACT_NONE else None)
         ctx.cfg = (stride, pad, act, slope, bias is not None, resid is not None)
         ctx.x_relu = bool(x_relu)
@@ -876,18 +882,9 @@ def conv2d_infer(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
     """Inference-only NHWC convolution with dilation (the frozen in-painting net's dilated residual blocks,
     generator.py:452-461): the tap list carries the dilated offsets, everything else is conv2d's forward."""
     x = _nhwc(pad_channels(x.detach(), 8))
-    n, h, w, cx = x.shape
-    cout, cin, kh, kw = weight.shape
-    if cx < cin:
-        raise ValueError(f"conv2d_infer: input has {cx} channels < weight Cin {cin}")
-    ho = (h + 2 * padding - dilation * (kh - 1) - 1) // stride + 1
-    wo = (w + 2 * padding - dilation * (kw - 1) - 1) // stride + 1
-    wp = pack_weight(weight, None, x.dtype, _roundup(cout, 128), cx, 0)
-    bp = bias.detach().float().contiguous() if bias is not None else None
-    out = torch.empty((n, ho, wo, cout), dtype=x.dtype, device=x.device)
-    _launch_conv(x, wp, out, bp, fwd_taps(kh, kw, padding, dilation), Hj=ho, Wj=wo, isy=stride, isx=stride,
-                 cout=cout, cout_gemm=cout, act=act, slope=slope, resid=_nhwc(resid) if resid is not None else None)
-    return out
+    if x.shape[3] < weight.shape[1]:
+        raise ValueError(f"conv2d_infer: input has {x.shape[3]} channels < weight Cin {weight.shape[1]}")
+    return _conv_forward("conv2d_infer", x, weight, bias, resid, stride, padding, dilation, act, slope)
 
 
 def conv_transpose2d_infer(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
@@ -1524,7 +1521,7 @@ class _AssembleFn(torch.autograd.Function):
 def assemble_nhwc8(dst: torch.Tensor, n0: int, planar: torch.Tensor, image: Optional[torch.Tensor] = None, cf: int = 0) -> torch.Tensor:
     """Fill dst[n0 : n0 + N] ([*, H, W, 8] NHWC, compute dtype) with [planar fp32 NCHW maps | first cf channels of the NHWC
     `image` | zeros] per pixel, one launch; differentiable w.r.t. `image`."""
-    planar = planar.detach().float().contiguous()
+    planar = _f32_dense(planar)
     if image is None:
         n, _, h, w = planar.shape
         C.backend().mg_assemble_nhwc8(_p(planar), planar.shape[1], None, 0, 0, _p(dst[n0:n0 + n]), _dt(dst), n, h * w, _stream(dst))
@@ -1587,22 +1584,34 @@ def blend(bg, x, hair_mask, back_mask, *, act: int = ACT_NONE, slope: float = 0.
     return _BlendFn.apply(bg, x, hair_mask, back_mask, act, slope)
 
 
+# Lengths, in floats, of what the scalar losses' two-stage reductions write: one row of per-workgroup partial sums per term.  The kernels
+# index these buffers by their own constants; tests/test_ops_emulated.py holds each name here to the constexpr it mirrors.
+L1_MEAN_BLOCKS = 1024                                  # the grid cap of mg_l1_mean_fwd (a literal in csrc/mg_pointwise.hip)
+ORIENT_LOSS_BLOCKS, ORIENT_LOSS_TERMS = 1024, 3        # OL_BLOCKS (csrc/mg_glue.hip); orient, conf and the hair count
+COLOR_LOSS_BLOCKS, COLOR_LOSS_TERMS = 1024, 3          # CL_BLOCKS (csrc/mg_color_loss.hip); lab, rgb, background
+HAIR_LAB_BLOCKS, HAIR_LAB_TERMS = 1024, 7              # HL_BLOCKS, HL_TERMS (csrc/mg_hair_lab.hip)
+
+
+def _l1_mean_launch(a, b):
+    """mean |a - b| of two dense tensors of one shape and dtype as a 0-d fp32 tensor (mg_l1_mean_fwd)."""
+    out = torch.empty(1, dtype=torch.float32, device=a.device)
+    ws = torch.empty(L1_MEAN_BLOCKS, dtype=torch.float32, device=a.device)
+    C.backend().mg_l1_mean_fwd(_p(a), _p(b), _dt(a), a.numel(), _p(out), _p(ws), _stream(a))
+    return out.reshape(())
+
+
 class _L1MeanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
         if a.shape != b.shape or a.dtype != b.dtype:
             raise ValueError("l1_mean: tensors must agree in shape and dtype")
-        n = a.numel()
-        out = torch.empty(1, dtype=torch.float32, device=a.device)
-        ws = torch.empty(1024, dtype=torch.float32, device=a.device)
-        C.backend().mg_l1_mean_fwd(_p(a), _p(b), _dt(a), n, _p(out), _p(ws), _stream(a))
         ctx.save_for_backward(a, b)
-        return out.reshape(())
+        return _l1_mean_launch(a, b)
 
     @staticmethod
     def backward(ctx, g):
         a, b = ctx.saved_tensors
-        g = g.reshape(1).float().contiguous()
+        (g,) = _f32_grads(g)
         da = torch.empty_like(a)
         C.backend().mg_l1_mean_bwd(_p(a), _p(b), _p(g), _dt(a), a.numel(), _p(da), _stream(a))
         return da, None
@@ -1617,18 +1626,14 @@ class _L1HalvesFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t):
         half = t.shape[0] // 2
-        a, b = t[:half], t[half:]
-        out = torch.empty(1, dtype=torch.float32, device=t.device)
-        ws = torch.empty(1024, dtype=torch.float32, device=t.device)
-        C.backend().mg_l1_mean_fwd(_p(a), _p(b), _dt(t), a.numel(), _p(out), _p(ws), _stream(t))
         ctx.save_for_backward(t)
-        return out.reshape(())
+        return _l1_mean_launch(t[:half], t[half:])
 
     @staticmethod
     def backward(ctx, g):
         (t,) = ctx.saved_tensors
         half = t.shape[0] // 2
-        g = g.reshape(1).float().contiguous()
+        (g,) = _f32_grads(g)
         dt = torch.empty_like(t)
         C.backend().mg_l1_mean_bwd(_p(t[:half]), _p(t[half:]), _p(g), _dt(t), t[:half].numel(), _p(dt[:half]), _stream(t))
         dt[half:].zero_()
@@ -1666,20 +1671,44 @@ def l1_mean(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 # ----------------------------------------------------------------------------
 # per-pixel glue around the convolutions (mg_glue.hip): one launch each instead of chains of eager element-wise ops
 # ----------------------------------------------------------------------------
-def _plane_args(t: torch.Tensor):
-    """(pointer, sample stride in elements) of an fp32 [N, H, W] view whose rows are dense (a channel slice of an NCHW tensor)."""
-    if t.dtype != torch.float32 or t.dim() != 3 or t.stride(2) != 1 or t.stride(1) != t.shape[2]:
+def _rows_dense(t: torch.Tensor) -> bool:
+    """Are the rows of the [N, H, W] view `t` dense (as in a channel slice of an NCHW tensor)?  The sample stride is free."""
+    return t.dim() == 3 and t.stride(2) == 1 and t.stride(1) == t.shape[2]
+
+
+def _plane_args(t: Optional[torch.Tensor]):
+    """(pointer, sample stride in elements) of an fp32 [N, H, W] view whose rows are dense; (None, 0) for an absent plane."""
+    if t is None:
+        return None, 0
+    if t.dtype != torch.float32 or not _rows_dense(t):
         raise ValueError("expected an fp32 [N, H, W] view with dense rows")
     return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2])
 
 
+def _f32_dense(t: Optional[torch.Tensor]):
+    """`t` detached, fp32 and contiguous (None stays None): the tensor's own storage when it is all three already -- no copy, no launch."""
+    return None if t is None else t.detach().float().contiguous()
+
+
+def _f32_plane(t: Optional[torch.Tensor], what: str, nhw) -> torch.Tensor:
+    """`t` detached and fp32 as a plane _plane_args takes: a view of its own storage when its rows are dense, a copy otherwise.
+    `what` ("operator: the operand") starts the error texts; `nhw`: the (N, H, W) the plane has to have."""
+    if t is None:
+        raise ValueError(f"{what} is needed for the selected terms")
+    t = t.detach().float()
+    if tuple(t.shape) != tuple(nhw):
+        raise ValueError(f"{what} {tuple(t.shape)} does not match [N, H, W] = {tuple(nhw)}")
+    return t if _rows_dense(t) else t.contiguous()
+
+
+def _f32_grads(*grads):
+    """The scalar gradients that reach a loss's backward pass, each as fp32; an absent one (None) stays absent."""
+    return [None if g is None else g.float() for g in grads]
+
+
 def planes_of(t: torch.Tensor):
     """The channel planes of an NCHW fp32 tensor as [N, H, W] views (no copy when the tensor is dense)."""
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    if not t.is_contiguous():
-        t = t.contiguous()
+    t = _f32_dense(t)
     return [t[:, c] for c in range(t.shape[1])]
 
 
@@ -1728,7 +1757,7 @@ class _PixelAffineFn(torch.autograd.Function):
         if a.numel() != pix or a.dtype != torch.float32 or (b is not None and (b.numel() != pix or b.dtype != torch.float32)):
             raise ValueError("pixel_affine: one fp32 value per pixel expected")
         y = torch.empty_like(x)
-        bf = bias.detach().float().contiguous() if bias is not None else None
+        bf = _f32_dense(bias)
         C.backend().mg_pixel_affine(_p(x), _p(a), _p(bf), _p(b) if bias is not None else None, _dt(x), pix, c, _p(y), _stream(x))
         ctx.save_for_backward(a, b if bias is not None else None)
         ctx.bias_dtype = bias.dtype if bias is not None else None
@@ -1765,8 +1794,7 @@ def bg_compose(image: Optional[torch.Tensor], noise: Optional[torch.Tensor], hai
     hair: fp32 [N, H, W] view; mode 0: back = 1 - maxpool_kxk(hair), mode 1: back = hair."""
     src = image if image is not None else noise
     n, _, H, W = src.shape
-    img = image.detach().float().contiguous() if image is not None else None
-    noi = noise.detach().float().contiguous() if noise is not None else None
+    img, noi = _f32_dense(image), _f32_dense(noise)
     hp, hs = _plane_args(hair.detach())
     inp = torch.empty((n, H, W, 8), dtype=dtype, device=src.device)
     back = torch.empty((n, 1, H, W), dtype=torch.float32, device=src.device)
@@ -1808,16 +1836,20 @@ def masked_mean_fill(x: torch.Tensor, lref: torch.Tensor, ltag: torch.Tensor) ->
     return _MaskedMeanFillFn.apply(x, lref, ltag)
 
 
-class _OrientLossFn(torch.autograd.Function):
+class _OrientTailFn(torch.autograd.Function):
+    """The tail of L1OLoss behind an arg-max: `fwd` / `bwd` name the two entry points (of one signature), n_out / n_ws are the lengths
+    in floats of the result and partial-sum buffers they write."""
+
     @staticmethod
-    def forward(ctx, conf_raw, idx, label, hair):
+    def forward(ctx, fwd, bwd, n_out, n_ws, conf_raw, idx, label, hair):
         n, h, w = conf_raw.shape
-        out = torch.empty(3, dtype=torch.float32, device=conf_raw.device)
-        ws = torch.empty(3 * 1024, dtype=torch.float32, device=conf_raw.device)
+        out = torch.empty(n_out, dtype=torch.float32, device=conf_raw.device)
+        ws = torch.empty(n_ws, dtype=torch.float32, device=conf_raw.device)
         hp, hs = _plane_args(hair)
-        C.backend().mg_orient_loss_fwd(_p(conf_raw), _p(idx), _p(label), label.shape[1], label.stride(0), hp, hs, n, h * w, _p(out), _p(ws),
-                                       _stream(conf_raw))
+        getattr(C.backend(), fwd)(_p(conf_raw), _p(idx), _p(label), label.shape[1], label.stride(0), hp, hs, n, h * w, _p(out), _p(ws),
+                                  _stream(conf_raw))
         ctx.save_for_backward(conf_raw, idx, label, hair, out)
+        ctx.bwd = bwd
         ctx.set_materialize_grads(False)
         return out[0], out[1]
 
@@ -1825,58 +1857,29 @@ class _OrientLossFn(torch.autograd.Function):
     def backward(ctx, g_orient, g_conf):
         conf_raw, idx, label, hair, out = ctx.saved_tensors
         if g_orient is None and g_conf is None:
-            return None, None, None, None
+            return (None,) * 8
         n, h, w = conf_raw.shape
-        fix = lambda g: None if g is None else (g if g.dtype == torch.float32 else g.float())
-        g_orient, g_conf = fix(g_orient), fix(g_conf)
+        g_orient, g_conf = _f32_grads(g_orient, g_conf)
         hp, hs = _plane_args(hair)
         d = torch.empty_like(conf_raw)
-        C.backend().mg_orient_loss_bwd(_p(conf_raw), _p(idx), _p(label), label.shape[1], label.stride(0), hp, hs, _p(g_orient), _p(g_conf),
-                                       _p(out), n, h * w, _p(d), _stream(conf_raw))
-        return d, None, None, None
+        getattr(C.backend(), ctx.bwd)(_p(conf_raw), _p(idx), _p(label), label.shape[1], label.stride(0), hp, hs, _p(g_orient), _p(g_conf),
+                                      _p(out), n, h * w, _p(d), _stream(conf_raw))
+        return (None,) * 4 + (d, None, None, None)
+
+
+def _orient_tail(who, fwd, bwd, n_out, n_ws, conf_raw, idx, label, hair):
+    return _OrientTailFn.apply(fwd, bwd, n_out, n_ws, conf_raw.contiguous(), idx.contiguous(), _f32_dense(label),
+                               _f32_plane(hair, who + ": the hair plane", conf_raw.shape))
 
 
 def orient_loss(conf_raw: torch.Tensor, idx: torch.Tensor, label: torch.Tensor, hair: torch.Tensor):
     """(orientation L1, confidence loss) of L1OLoss behind the Gabor arg-max (loss.py:352-385): conf_raw fp32 [N,H,W], idx u8 [N,H,W],
     label fp32 [N, 1 or 2, H, W] (0..255 angle map or (sin 2t, cos 2t) planes), hair fp32 [N, H, W] view.  Two launches forward, one backward."""
-    label = label.detach().float()
-    if not label.is_contiguous():
-        label = label.contiguous()
-    hair = hair.detach()
-    if hair.dtype != torch.float32:
-        hair = hair.float()
-    return _OrientLossFn.apply(conf_raw.contiguous(), idx.contiguous(), label, hair)
+    return _orient_tail("orient_loss", "mg_orient_loss_fwd", "mg_orient_loss_bwd", ORIENT_LOSS_TERMS, ORIENT_LOSS_TERMS * ORIENT_LOSS_BLOCKS,
+                        conf_raw, idx, label, hair)
 
 
 ORIENT_DOG_BLOCKS, ORIENT_DOG_WS_ROWS, ORIENT_DOG_OUT = 1024, 7, 8       # MGL_ORIENT_DOG_* (include/michigan_hip/losses/orient_dog.h)
-
-
-class _OrientDogLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, conf_raw, idx, label, hair):
-        n, h, w = conf_raw.shape
-        out = torch.empty(ORIENT_DOG_OUT, dtype=torch.float32, device=conf_raw.device)
-        ws = torch.empty(ORIENT_DOG_WS_ROWS * ORIENT_DOG_BLOCKS, dtype=torch.float32, device=conf_raw.device)
-        hp, hs = _plane_args(hair)
-        C.backend().mgl_orient_dog_fwd(_p(conf_raw), _p(idx), _p(label), label.shape[1], label.stride(0), hp, hs, n, h * w, _p(out), _p(ws),
-                                       _stream(conf_raw))
-        ctx.save_for_backward(conf_raw, idx, label, hair, out)
-        ctx.set_materialize_grads(False)
-        return out[0], out[1]
-
-    @staticmethod
-    def backward(ctx, g_orient, g_conf):
-        conf_raw, idx, label, hair, out = ctx.saved_tensors
-        if g_orient is None and g_conf is None:
-            return None, None, None, None
-        n, h, w = conf_raw.shape
-        fix = lambda g: None if g is None else (g if g.dtype == torch.float32 else g.float())
-        g_orient, g_conf = fix(g_orient), fix(g_conf)
-        hp, hs = _plane_args(hair)
-        d = torch.empty_like(conf_raw)
-        C.backend().mgl_orient_dog_bwd(_p(conf_raw), _p(idx), _p(label), label.shape[1], label.stride(0), hp, hs, _p(g_orient), _p(g_conf),
-                                       _p(out), n, h * w, _p(d), _stream(conf_raw))
-        return d, None, None, None
 
 
 def orient_loss_dog(conf_raw: torch.Tensor, idx: torch.Tensor, label: torch.Tensor, hair: torch.Tensor):
@@ -1886,13 +1889,8 @@ def orient_loss_dog(conf_raw: torch.Tensor, idx: torch.Tensor, label: torch.Tens
     samples of the batch; with no positive response under the hair anywhere both losses are NaN, as in the reference.  Under one process
     per GPU that maximum is the rank's own, which is what a replica of the reference's DataParallel computes: no collective is needed.
     Three launches forward, one backward, no read-back."""
-    label = label.detach().float()
-    if not label.is_contiguous():
-        label = label.contiguous()
-    hair = hair.detach()
-    if hair.dtype != torch.float32:
-        hair = hair.float()
-    return _OrientDogLossFn.apply(conf_raw.contiguous(), idx.contiguous(), label, hair)
+    return _orient_tail("orient_loss_dog", "mgl_orient_dog_fwd", "mgl_orient_dog_bwd", ORIENT_DOG_OUT, ORIENT_DOG_WS_ROWS * ORIENT_DOG_BLOCKS,
+                        conf_raw, idx, label, hair)
 
 
 COLOR_LAB, COLOR_RGB, COLOR_BACKGROUND = 1, 2, 4      # `flags` bits of mg_color_loss_*
@@ -1903,9 +1901,9 @@ class _ColorLossFn(torch.autograd.Function):
     def forward(ctx, img, real, back, flags):
         img = _nhwc(img)
         n, h, w, c = img.shape
-        out = torch.empty(3, dtype=torch.float32, device=img.device)
-        ws = torch.empty(3 * 1024, dtype=torch.float32, device=img.device)
-        bp, bs = _plane_args(back) if back is not None else (None, 0)
+        out = torch.empty(COLOR_LOSS_TERMS, dtype=torch.float32, device=img.device)
+        ws = torch.empty(COLOR_LOSS_TERMS * COLOR_LOSS_BLOCKS, dtype=torch.float32, device=img.device)
+        bp, bs = _plane_args(back)
         C.backend().mg_color_loss_fwd(_p(img), _p(real), real.stride(0), bp, bs, _dt(img), n, h, w, c, flags, _p(out), _p(ws), _stream(img))
         ctx.save_for_backward(img, real, back)
         ctx.flags = flags
@@ -1918,9 +1916,8 @@ class _ColorLossFn(torch.autograd.Function):
         if g_lab is None and g_rgb is None and g_back is None:
             return None, None, None, None
         n, h, w, c = img.shape
-        fix = lambda g: None if g is None else (g if g.dtype == torch.float32 else g.float())
-        g_lab, g_rgb, g_back = fix(g_lab), fix(g_rgb), fix(g_back)
-        bp, bs = _plane_args(back) if back is not None else (None, 0)
+        g_lab, g_rgb, g_back = _f32_grads(g_lab, g_rgb, g_back)
+        bp, bs = _plane_args(back)
         d = torch.empty_like(img)
         C.backend().mg_color_loss_bwd(_p(img), _p(real), real.stride(0), bp, bs, _p(g_lab), _p(g_rgb), _p(g_back), _dt(img), n, h, w, c,
                                       ctx.flags, _p(d), _stream(img))
@@ -1939,24 +1936,8 @@ def color_losses(fake: torch.Tensor, real: torch.Tensor, back: Optional[torch.Te
     if fake.dim() != 4 or real.dim() != 4 or real.shape[1] != 3 or fake.shape[-1] < 3 or \
             (fake.shape[0], fake.shape[1], fake.shape[2]) != (real.shape[0], real.shape[2], real.shape[3]):
         raise ValueError(f"color_losses: NHWC image {tuple(fake.shape)} does not match the NCHW target {tuple(real.shape)}")
-    real = real.detach()
-    if real.dtype != torch.float32:
-        real = real.float()
-    if not real.is_contiguous():
-        real = real.contiguous()
-    if flags & COLOR_BACKGROUND:
-        if back is None:
-            raise ValueError("color_losses: COLOR_BACKGROUND needs the background plane")
-        back = back.detach()
-        if back.dtype != torch.float32:
-            back = back.float()
-        if tuple(back.shape) != (fake.shape[0], fake.shape[1], fake.shape[2]):
-            raise ValueError(f"color_losses: background plane {tuple(back.shape)} does not match the image")
-        if back.stride(2) != 1 or back.stride(1) != back.shape[2]:
-            back = back.contiguous()
-    else:
-        back = None
-    return _ColorLossFn.apply(fake, real, back, flags)
+    back = _f32_plane(back, "color_losses: the background plane", fake.shape[:3]) if flags & COLOR_BACKGROUND else None
+    return _ColorLossFn.apply(fake, _f32_dense(real), back, flags)
 
 
 HAIR_LAB, HAIR_BACKGROUND = 1, 2                      # `flags` bits of mg_hair_lab_*
@@ -1969,9 +1950,8 @@ class _HairLabLossFn(torch.autograd.Function):
         n, h, w, c = img.shape
         out = torch.empty(2, dtype=torch.float32, device=img.device)
         stats = torch.empty(4 * n, dtype=torch.float32, device=img.device) if flags & HAIR_LAB else None
-        ws = torch.empty(7 * max(1024, n), dtype=torch.float32, device=img.device)
-        plane = lambda t: _plane_args(t) if t is not None else (None, 0)
-        (fp, fs), (rp, rs), (bp, bs) = plane(hair_tag), plane(hair_ref), plane(back)
+        ws = torch.empty(HAIR_LAB_TERMS * max(HAIR_LAB_BLOCKS, n), dtype=torch.float32, device=img.device)
+        (fp, fs), (rp, rs), (bp, bs) = _plane_args(hair_tag), _plane_args(hair_ref), _plane_args(back)
         C.backend().mg_hair_lab_fwd(_p(img), _p(ref), ref.stride(0) if ref is not None else 0, fp, fs, rp, rs,
                                     _p(tgt), tgt.stride(0) if tgt is not None else 0, bp, bs, _dt(img), n, h, w, c, flags,
                                     _p(out), _p(stats), _p(ws), _stream(img))
@@ -1986,10 +1966,8 @@ class _HairLabLossFn(torch.autograd.Function):
         if g_hair is None and g_back is None:
             return (None,) * 7
         n, h, w, c = img.shape
-        fix = lambda g: None if g is None else (g if g.dtype == torch.float32 else g.float())
-        g_hair, g_back = fix(g_hair), fix(g_back)
-        plane = lambda t: _plane_args(t) if t is not None else (None, 0)
-        (fp, fs), (bp, bs) = plane(hair_tag), plane(back)
+        g_hair, g_back = _f32_grads(g_hair, g_back)
+        (fp, fs), (bp, bs) = _plane_args(hair_tag), _plane_args(back)
         d = torch.empty_like(img)
         C.backend().mg_hair_lab_bwd(_p(img), fp, fs, _p(tgt), tgt.stride(0) if tgt is not None else 0, bp, bs, _p(stats),
                                     _p(g_hair), _p(g_back), _dt(img), n, h, w, c, ctx.flags, _p(d), _stream(img))
@@ -2017,27 +1995,16 @@ def hair_lab_losses(fake: torch.Tensor, image_ref: Optional[torch.Tensor], hair_
             raise ValueError("hair_lab_losses: %s is needed for the selected terms" % name)
         if t.dim() != 4 or tuple(t.shape) != (n, 3, h, w):
             raise ValueError(f"hair_lab_losses: NHWC image {tuple(fake.shape)} does not match the NCHW {name} {tuple(t.shape)}")
-        t = t.detach()
-        if t.dtype != torch.float32:
-            t = t.float()
-        return t if t.is_contiguous() else t.contiguous()
-
-    def plane(t, name):
-        if t is None:
-            raise ValueError("hair_lab_losses: %s is needed for the selected terms" % name)
-        t = t.detach()
-        if t.dtype != torch.float32:
-            t = t.float()
-        if tuple(t.shape) != (n, h, w):
-            raise ValueError(f"hair_lab_losses: {name} {tuple(t.shape)} does not match the image")
-        return t if (t.stride(2) == 1 and t.stride(1) == t.shape[2]) else t.contiguous()
+        return _f32_dense(t)
 
     if flags & HAIR_LAB:
-        image_ref, hair_tag, hair_ref = image(image_ref, "image_ref"), plane(hair_tag, "the tag hair plane"), plane(hair_ref, "the reference hair plane")
+        image_ref = image(image_ref, "image_ref")
+        hair_tag = _f32_plane(hair_tag, "hair_lab_losses: the tag hair plane", (n, h, w))
+        hair_ref = _f32_plane(hair_ref, "hair_lab_losses: the reference hair plane", (n, h, w))
     else:
         image_ref = hair_tag = hair_ref = None
     if flags & HAIR_BACKGROUND:
-        image_tag, back = image(image_tag, "image_tag"), plane(back, "the background plane")
+        image_tag, back = image(image_tag, "image_tag"), _f32_plane(back, "hair_lab_losses: the background plane", (n, h, w))
     else:
         image_tag = back = None
     return _HairLabLossFn.apply(fake, image_ref, hair_tag, hair_ref, image_tag, back, flags)
@@ -2051,10 +2018,9 @@ def _feat_desc(x, s, t, masks, flags, out=None, coef=None, ws=None):
     n, h, w, c = x.shape
     d.x, d.s, d.t = x.data_ptr(), (s.data_ptr() if s is not None else None), (t.data_ptr() if t is not None else None)
     for name, m in zip(("mask_x", "mask_s", "mask_t"), masks):
-        if m is not None:
-            ptr, stride = _plane_args(m)
-            setattr(d, name, ptr)
-            setattr(d, name + "_nstride", stride)
+        ptr, stride = _plane_args(m)
+        setattr(d, name, ptr)
+        setattr(d, name + "_nstride", stride)
     d.P, d.dtype, d.N, d.C, d.flags = h * w, _dt(x), n, c, flags
     d.out, d.coef, d.ws = (None if out is None else out.data_ptr()), coef.data_ptr(), (None if ws is None else ws.data_ptr())
     return d
@@ -2079,8 +2045,7 @@ class _FeatMomentLossFn(torch.autograd.Function):
         x, t, mask_x, mask_t, coef = ctx.saved_tensors
         if g_style is None and g_content is None:
             return (None,) * 7
-        fix = lambda g: None if g is None else (g if g.dtype == torch.float32 else g.float())
-        g_style, g_content = fix(g_style), fix(g_content)
+        g_style, g_content = _f32_grads(g_style, g_content)
         d = torch.empty_like(x)
         C.backend().mg_feat_moment_loss_bwd(_feat_desc(x, None, t, (mask_x, None, mask_t), ctx.flags, coef=coef), _p(g_style), _p(g_content),
                                             _p(d), _stream(x))
@@ -2113,27 +2078,19 @@ def feat_moment_loss(x: torch.Tensor, s: Optional[torch.Tensor], t: Optional[tor
         f = f.detach()
         return _nhwc((f if f.dtype == x.dtype else f.to(x.dtype)).permute(0, 2, 3, 1))
 
-    def plane(m, name):
-        m = m.detach()
-        if m.dtype != torch.float32:
-            m = m.float()
-        if tuple(m.shape) != (n, h, w):
-            raise ValueError(f"feat_moment_loss: {name} {tuple(m.shape)} does not match the features")
-        return m if (m.stride(2) == 1 and m.stride(1) == m.shape[2]) else m.contiguous()
-
     if flags & FEAT_STYLE:
         s = feats(s, "the style features")
         if (mask_x is None) != (mask_s is None):
             raise ValueError("feat_moment_loss: mask_x and mask_s come together")
         if mask_x is not None:
-            mask_x, mask_s = plane(mask_x, "mask_x"), plane(mask_s, "mask_s")
+            mask_x, mask_s = _f32_plane(mask_x, "feat_moment_loss: mask_x", (n, h, w)), _f32_plane(mask_s, "feat_moment_loss: mask_s", (n, h, w))
         elif h * w < 2:
             raise ValueError("feat_moment_loss: the unbiased variance needs at least two pixels")
     else:
         s = mask_x = mask_s = None
     if flags & FEAT_CONTENT:
         t = feats(t, "the content features")
-        mask_t = plane(mask_t, "mask_t") if mask_t is not None else None
+        mask_t = _f32_plane(mask_t, "feat_moment_loss: mask_t", (n, h, w)) if mask_t is not None else None
     else:
         t = mask_t = None
     return _FeatMomentLossFn.apply(x.permute(0, 2, 3, 1), s, t, mask_x, mask_s, mask_t, flags)
@@ -2192,7 +2149,7 @@ class _HingeFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight = ctx.saved_tensors
-        g = g.reshape(1).float().contiguous()
+        (g,) = _f32_grads(g)
         dx = torch.empty_like(x)
         C.backend().mg_hinge_bwd(_p(x), _p(weight), _p(g), _dt(x), x.numel(), ctx.mode, _p(dx), _stream(x))
         return dx, None, None
@@ -2212,7 +2169,7 @@ def hinge_loss(logits: torch.Tensor, weight: Optional[torch.Tensor], mode: int) 
 
 def wide_edge_weight(label: torch.Tensor, h: int, w: int, wide: float, th: float = 0.06) -> torch.Tensor:
     """GANLoss.get_weight_mask (loss.py:60-89) for one logit resolution: label [N,1,Hl,Wl] in {0,1} -> fp32 [N,1,h,w]."""
-    label = label.detach().float().contiguous()
+    label = _f32_dense(label)
     n, c, hl, wl = label.shape
     if c != 1:
         raise ValueError("wide_edge_weight: the label must have one channel")
@@ -2222,16 +2179,20 @@ def wide_edge_weight(label: torch.Tensor, h: int, w: int, wide: float, th: float
     return out
 
 
+def _rotated_grid(theta: torch.Tensor):
+    """(x', y') of the 17x17 tap grid turned by each angle of `theta` (fp32 [K]): two fp32 [K, 17, 17]; x runs along rows."""
+    r = torch.arange(-8, 9, dtype=torch.float32)
+    x = r.view(-1, 1).expand(17, 17)
+    y = r.view(1, -1).expand(17, 17)
+    theta = theta.view(-1, 1, 1)
+    return x * torch.cos(theta) + y * torch.sin(theta), -x * torch.sin(theta) + y * torch.cos(theta)
+
+
 def gabor_bank(device=None) -> torch.Tensor:
     """The 32 oriented 17x17 Gabor kernels of the orientation loss, fp32 [32, 17, 17]
     (loss.py:215-243: sigma_x 2, sigma_y 3, lambda 4, psi 0, theta_k = pi k / 32; x runs along rows)."""
     import math
-    r = torch.arange(-8, 9, dtype=torch.float32)
-    x = r.view(-1, 1).expand(17, 17)
-    y = r.view(1, -1).expand(17, 17)
-    theta = (math.pi * torch.arange(32, dtype=torch.float32) / 32).view(-1, 1, 1)
-    xt = x * torch.cos(theta) + y * torch.sin(theta)
-    yt = -x * torch.sin(theta) + y * torch.cos(theta)
+    xt, yt = _rotated_grid(math.pi * torch.arange(32, dtype=torch.float32) / 32)
     gb = torch.exp(-0.5 * (xt ** 2 / 2.0 ** 2 + yt ** 2 / 3.0 ** 2)) * torch.cos(2 * math.pi / 4.0 * xt)
     return gb.contiguous().to(device) if device is not None else gb.contiguous()
 
@@ -2272,12 +2233,7 @@ def dog_bank(device=None) -> torch.Tensor:
     (cal_orientation.py:18-44: sigma_h 1, sigma_l 2, sigma_y 2, theta_k = pi k / 32, normalised by 1/sigma_h - 1/sigma_l;
     x runs along rows).  With this bank mg_gabor_argmax_fwd is orient.calOrientation (cal_orientation.py:60-80)."""
     import math
-    r = torch.arange(-8, 9, dtype=torch.float32)
-    x = r.view(-1, 1).expand(17, 17)
-    y = r.view(1, -1).expand(17, 17)
-    theta = torch.tensor([math.pi * k / 32 for k in range(32)], dtype=torch.float32).view(-1, 1, 1)    # rounded once, as the reference's
-    xt = x * torch.cos(theta) + y * torch.sin(theta)
-    yt = -x * torch.sin(theta) + y * torch.cos(theta)
+    xt, yt = _rotated_grid(torch.tensor([math.pi * k / 32 for k in range(32)], dtype=torch.float32))    # rounded once, as the reference's
     gb = (torch.exp(-0.5 * (xt ** 2 / 1.0 ** 2 + yt ** 2 / 2.0 ** 2)) / 1.0
           - torch.exp(-0.5 * (xt ** 2 / 2.0 ** 2 + yt ** 2 / 2.0 ** 2)) / 2.0) / (1.0 / 1.0 - 1.0 / 2.0)
     return gb.contiguous().to(device) if device is not None else gb.contiguous()
@@ -2305,14 +2261,22 @@ def gaussian_taps(sigma: float) -> torch.Tensor:
     return (t / t.sum()).float().contiguous()
 
 
-_ORIENT_TABLES = {}
+_DEVICE_TABLES = {}
 
 
-def _orient_tables(device, sigma: float):
-    key = (str(device), float(sigma))
-    if key not in _ORIENT_TABLES:
-        _ORIENT_TABLES[key] = (orient_trig_table().to(device), gaussian_taps(sigma).to(device))
-    return _ORIENT_TABLES[key]
+def _device_table(device, key, make):
+    """make(): a small constant table the kernels read, built once per (device, key) and kept."""
+    key = (str(device),) + key
+    if key not in _DEVICE_TABLES:
+        _DEVICE_TABLES[key] = make()
+    return _DEVICE_TABLES[key]
+
+
+def _check_nhw(who: str, shape):
+    """The kernels over [N, H, W] planes index with 32-bit integers."""
+    n, h, w = shape
+    if n < 1 or h < 1 or w < 1 or n * h * w >= 1 << 31:
+        raise ValueError(f"{who}: bad geometry {tuple(shape)} (N H W must be in [1, 2^31))")
 
 
 def orient_smooth(conf: torch.Tensor, idx: torch.Tensor, mask: torch.Tensor, sigma: float = 4.0, want_angle: bool = False):
@@ -2325,7 +2289,7 @@ def orient_smooth(conf: torch.Tensor, idx: torch.Tensor, mask: torch.Tensor, sig
     n, h, w = conf.shape
     if n < 1 or h <= ORIENT_RADIUS or w <= ORIENT_RADIUS:
         raise ValueError(f"orient_smooth: H and W must be at least {ORIENT_RADIUS + 1} (one reflection reaches every tap), got {h} x {w}")
-    trig, taps = _orient_tables(conf.device, sigma)
+    trig, taps = _device_table(conf.device, ("orient", float(sigma)), lambda: (orient_trig_table().to(conf.device), gaussian_taps(sigma).to(conf.device)))
     conf, idx, mask = conf.contiguous(), idx.contiguous(), mask.contiguous()
     out = torch.empty((n, h, w), dtype=torch.uint8, device=conf.device)
     angle = torch.empty((n, h, w), dtype=torch.float32, device=conf.device) if want_angle else None
@@ -2342,16 +2306,6 @@ def stroke_rgb_table() -> torch.Tensor:
     return ((v + 1) / 2.0 * 255.0).to(torch.uint8).contiguous()        # np.uint8 of a value in [0, 255]: truncation
 
 
-_STROKE_TABLES = {}
-
-
-def _stroke_tables(device):
-    key = str(device)
-    if key not in _STROKE_TABLES:
-        _STROKE_TABLES[key] = (dog_bank().to(device), stroke_rgb_table().to(device))
-    return _STROKE_TABLES[key]
-
-
 def stroke_orient(stroke: torch.Tensor, want_idx: bool = False, want_conf: bool = False, bank: Optional[torch.Tensor] = None):
     """orient().stroke_to_orient (cal_orient_stroke.py:85-121, 133-149) in one launch (mg_stroke_orient): stroke u8 [N,H,W], non-zero =
     stroke -> the RGB-coded orientation picture u8 [N,H,W,3], black outside the stroke (and the filter index u8 / the confidence
@@ -2359,9 +2313,8 @@ def stroke_orient(stroke: torch.Tensor, want_idx: bool = False, want_conf: bool 
     if stroke.dim() != 3 or stroke.dtype != torch.uint8:
         raise ValueError(f"stroke_orient: stroke must be uint8 [N,H,W], got {stroke.dtype} {tuple(stroke.shape)}")
     n, h, w = stroke.shape
-    if n < 1 or h < 1 or w < 1 or n * h * w >= 1 << 31:
-        raise ValueError(f"stroke_orient: bad geometry {tuple(stroke.shape)} (N H W must be in [1, 2^31))")
-    dog, table = _stroke_tables(stroke.device)
+    _check_nhw("stroke_orient", stroke.shape)
+    dog, table = _device_table(stroke.device, ("stroke",), lambda: (dog_bank().to(stroke.device), stroke_rgb_table().to(stroke.device)))
     if bank is None:
         bank = dog
     elif bank.dtype != torch.float32 or tuple(bank.shape) != (32, 17, 17) or bank.device != stroke.device:
@@ -2393,8 +2346,9 @@ def brush_u8(canvas: torch.Tensor, segs: torch.Tensor) -> torch.Tensor:
     if segs.dim() != 2 or segs.shape[1] != 8 or segs.dtype != torch.int32 or segs.device != canvas.device:
         raise ValueError(f"brush_u8: segs must be int32 [S,8] on {canvas.device}, got {segs.dtype} {tuple(segs.shape)} on {segs.device}")
     n, h, w = canvas.shape
-    if n < 1 or not (1 <= h <= BRUSH_MAX_COORD + 1 and 1 <= w <= BRUSH_MAX_COORD + 1) or n * h * w >= 1 << 31:
-        raise ValueError(f"brush_u8: bad geometry {tuple(canvas.shape)} (H, W in [1, {BRUSH_MAX_COORD + 1}], N H W < 2^31)")
+    if h > BRUSH_MAX_COORD + 1 or w > BRUSH_MAX_COORD + 1:
+        raise ValueError(f"brush_u8: bad geometry {tuple(canvas.shape)} (H, W in [1, {BRUSH_MAX_COORD + 1}])")
+    _check_nhw("brush_u8", canvas.shape)
     segs = segs.contiguous()
     C.backend().mge_brush_u8(_p(canvas), _p(segs), segs.shape[0], n, h, w, _stream(canvas))
     return canvas
@@ -2417,8 +2371,7 @@ def morph_u8(src: torch.Tensor, elem: torch.Tensor, anchor, op: int) -> torch.Te
         raise ValueError(f"morph_u8: anchor (x {ax}, y {ay}) outside the {kh} x {kw} element")
     if op not in (MORPH_DILATE, MORPH_ERODE):
         raise ValueError(f"morph_u8: op must be MORPH_DILATE or MORPH_ERODE, got {op}")
-    if n < 1 or h < 1 or w < 1 or n * h * w >= 1 << 31:
-        raise ValueError(f"morph_u8: bad geometry {tuple(src.shape)} (N H W must be in [1, 2^31))")
+    _check_nhw("morph_u8", src.shape)
     src, elem = src.contiguous(), elem.contiguous()
     dst = torch.empty((n, h, w), dtype=torch.uint8, device=src.device)
     C.backend().mge_morph_u8(_p(src), _p(elem), kh, kw, ay, ax, op, _p(dst), n, h, w, _stream(src))
@@ -2473,8 +2426,7 @@ def orient_distance_u8(a: torch.Tensor, b: torch.Tensor, mask: torch.Tensor) -> 
             raise ValueError(f"orient_distance_u8: {name} must be uint8 {tuple(a.shape)} on {a.device}, got "
                              + ("None" if t is None else f"{t.dtype} {tuple(t.shape)} on {t.device}"))
     n, h, w = a.shape
-    if n < 1 or h < 1 or w < 1 or n * h * w >= 1 << 31:
-        raise ValueError(f"orient_distance_u8: bad geometry {tuple(a.shape)} (N H W must be in [1, 2^31))")
+    _check_nhw("orient_distance_u8", a.shape)
     a, b, mask = a.contiguous(), b.contiguous(), mask.contiguous()
     out = torch.empty((n, 2), dtype=torch.int64, device=a.device)
     C.backend().mgq_orient_distance_u8(_p(a), _p(b), _p(mask), _p(out), n, h, w, _stream(a))
@@ -2494,14 +2446,8 @@ def interp_nearest_table(src: int, dst: int, device=None) -> Optional[torch.Tens
     return t.to(device) if device is not None else t
 
 
-_INTERP_TABLES = {}
-
-
 def _interp_table(src: int, dst: int, device):
-    key = (int(src), int(dst), str(device))
-    if key not in _INTERP_TABLES:
-        _INTERP_TABLES[key] = interp_nearest_table(src, dst, device)
-    return _INTERP_TABLES[key]
+    return _device_table(device, ("interp", int(src), int(dst)), lambda: interp_nearest_table(src, dst, device))
 
 
 def _planes(name, t, c, n, h, w):

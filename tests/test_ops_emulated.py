@@ -321,6 +321,42 @@ def test_glue_contracts_match_the_eager_chains_they_replace(emulator_backend):
     assert (gg - gw).abs().max() < 1e-6 * max(1.0, float(gw.abs().max()))
 
 
+def test_loss_workspace_sizes_mirror_the_kernels_constants():
+    """ops sizes the scalar losses' partial-sum workspaces, the kernels index them by constexprs of their own: neither side moves alone."""
+    import os
+    import re
+    from michigan_amd import ops
+
+    def constexprs(source):
+        with open(os.path.join(os.path.dirname(ops.__file__), "csrc", source)) as fh:
+            return {name: int(value) for name, value in re.findall(r"^constexpr int (\w+) = (\d+);", fh.read(), re.M)}
+    assert constexprs("mg_glue.hip")["OL_BLOCKS"] == ops.ORIENT_LOSS_BLOCKS
+    assert constexprs("mg_color_loss.hip")["CL_BLOCKS"] == ops.COLOR_LOSS_BLOCKS
+    hair = constexprs("mg_hair_lab.hip")
+    assert (hair["HL_BLOCKS"], hair["HL_TERMS"]) == (ops.HAIR_LAB_BLOCKS, ops.HAIR_LAB_TERMS)
+
+
+def test_operand_normalisers_keep_an_operand_that_is_already_in_form():
+    """No copy and no launch for an operand already detached-able, fp32 and dense: the normalisers hand back the input's own storage
+    (the training step is host-bound: every copy here is a launch per loss per step).  Anything else is copied into form."""
+    from michigan_amd import ops
+    sem = torch.rand(2, 3, 5, 7)
+    assert ops._f32_dense(sem).data_ptr() == sem.data_ptr() and ops._f32_dense(None) is None
+    view = sem.permute(0, 1, 3, 2)
+    assert ops._f32_dense(view).is_contiguous() and torch.equal(ops._f32_dense(view), view)
+    for plane in (sem[:, 1], sem[:, 1].contiguous(), sem[:1, 2]):               # dense rows, any sample stride
+        got = ops._f32_plane(plane, "test: plane", plane.shape)
+        assert got.data_ptr() == plane.data_ptr() and got.stride() == plane.stride()
+        assert ops._plane_args(got) == (plane.data_ptr(), plane.stride(0) if plane.shape[0] > 1 else 35)
+    for plane in (sem[:, :, :, 0], sem[:, 1].double(), sem[:, 1, :, ::2]):         # rows not dense / not fp32: copied
+        got = ops._f32_plane(plane, "test: plane", plane.shape)
+        assert got.dtype == torch.float32 and got.is_contiguous() and torch.equal(got, plane.float())
+    assert ops._plane_args(None) == (None, 0)
+    g = torch.tensor(2.0)
+    kept, cast, absent = ops._f32_grads(g, g.bfloat16(), None)
+    assert kept is g and cast.dtype == torch.float32 and float(cast) == 2.0 and absent is None
+
+
 def test_flatadam_adopts_gradients_detached_from_its_arena(emulator_backend):
     """`module.zero_grad()` (set_to_none) detaches p.grad from the flat gradient arena; the next backward then leaves the
     gradient in a fresh tensor the arena-wide Adam kernel never sees.  step() folds such gradients back in."""
