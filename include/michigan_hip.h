@@ -476,7 +476,7 @@ int mg_orient_loss_bwd(const float* conf_raw, const uint8_t* idx, const float* l
                        int32_t N, int64_t HW, float* dconf, void* stream);
 
 /* The image-space L1 terms of the generator objective in one pass over the generated and the target image (mg_color_loss.hip):
- * LabColorLoss.forward (loss.py:403-532, called at pix2pix_model.py:331-336; balance_Lab off), criterionRGBL1 = nn.L1Loss
+ * LabColorLoss.forward (loss.py:403-532, called at pix2pix_model.py:331-336; balance_Lab off -- on: michigan_hip/losses/lab_balance.h), criterionRGBL1 = nn.L1Loss
  * (pix2pix_model.py:324-329) and RGBBackgroundL1Loss.forward (loss.py:388-400, called at pix2pix_model.py:317-322).
  * img: the generated image, NHWC [N,H,W,C] in `dtype` with RGB in channels 0..2 (C >= 3; the layout of mg_gabor_argmax_fwd); real: the
  * target, fp32, three dense planes [H,W] per sample, sample n at real + n * real_nstride; back: the background plane m (channel 0 of the
@@ -498,7 +498,7 @@ int mg_color_loss_bwd(const void* img, const float* real, int64_t real_nstride, 
                       int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flags, void* dimg, void* stream);
 
 /* The two image-space terms of the unpaired training stage (curr_step = 2) in one pass over the generated image (mg_hair_lab.hip):
- * HairAvgLabLoss.forward (loss.py:534-621, called at pix2pix_model.py:356-358; balance_Lab off) and RGBBackgroundL1Loss.forward
+ * HairAvgLabLoss.forward (loss.py:534-621, called at pix2pix_model.py:356-358; balance_Lab off -- on: michigan_hip/losses/lab_balance.h) and RGBBackgroundL1Loss.forward
  * (loss.py:388-400, called at pix2pix_model.py:362-363).
  * img: the generated image as in mg_color_loss_fwd (NHWC [N,H,W,C] in `dtype`, RGB in channels 0..2).  ref (= image_ref) and tgt
  * (= image_tag): fp32, three dense planes [H,W] per sample at a sample stride.  hair_tag (m_f), hair_ref (m_r), back (m_b): fp32 planes

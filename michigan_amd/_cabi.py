@@ -216,6 +216,15 @@ _LOSS_PROTOS = {
     "mgl_orient_dog_bwd": ([_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp], _i32),
 }
 _EXTENSION_PROTOS = dict(_EDIT_PROTOS, **_QUALITY_PROTOS, **_LOSS_PROTOS)
+# include/michigan_hip/losses/lab_balance.h: the colour-balance extension group (prefix mgc_), the colour and hair-Lab passes under
+# --balance_Lab.  A table of its own beside the three above: the argument lists of mg_color_loss_* with (hair, hair_nstride, table)
+# after the background plane, of mg_hair_lab_fwd with the table after the background plane, and of mg_hair_lab_bwd as it is.
+_COLOR_PROTOS = {
+    "mgc_color_loss_balanced_fwd": ([_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp], _i32),
+    "mgc_color_loss_balanced_bwd": ([_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
+    "mgc_hair_lab_balanced_fwd": ([_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp], _i32),
+    "mgc_hair_lab_balanced_bwd": ([_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
+}
 EXPORTED_SYMBOLS = tuple(_PROTOS)              # the whole ABI: tests/test_cabi_host.py holds it to the headers and to the library's exports
 _NO_STATUS = {"mg_wgrad_det_workspace", "mg_norm_apply2_supported", "mg_grad_slot_blocks", "mg_pack_job_blocks", "mg_sn_layer_blocks", "mg_stats_workspace", "mg_sizeof_desc", "mg_abi_version", "mg_last_error", "mg_noise_field_len", "mg_bicubic_ksize",
               "mg_feat_moment_workspace"}
@@ -249,7 +258,7 @@ class HipBackend:
         # torch must already have loaded its libamdhip64 so that we bind to the same runtime.
         import torch  # noqa: F401
         self._lib = ctypes.CDLL(path)
-        for fn, (argtypes, restype) in list(_PROTOS.items()) + list(_EXTENSION_PROTOS.items()):
+        for fn, (argtypes, restype) in list(_PROTOS.items()) + list(_EXTENSION_PROTOS.items()) + list(_COLOR_PROTOS.items()):
             f = getattr(self._lib, fn)          # AttributeError if a symbol is missing
             f.argtypes, f.restype = argtypes, restype
         if self._lib.mg_abi_version() != MG_ABI_VERSION:
@@ -258,7 +267,7 @@ class HipBackend:
             raise RuntimeError("ctypes mirror of the descriptor structs is out of sync with include/michigan_hip.h")
 
     def __getattr__(self, fn):
-        if fn not in _PROTOS and fn not in _EXTENSION_PROTOS:
+        if fn not in _PROTOS and fn not in _EXTENSION_PROTOS and fn not in _COLOR_PROTOS:
             raise AttributeError(fn)
         raw = getattr(self._lib, fn)
         if fn in _NO_STATUS or fn in _EXTENSION_NO_STATUS:

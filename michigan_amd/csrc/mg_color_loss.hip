@@ -11,6 +11,13 @@
 //   color_loss_bwd_kernel       dimg = g_lab dlab + g_rgb drgb + g_back dback in the image's dtype and layout, padding channels zero
 // The eager spelling is ~40 launches per call, six of them boolean-mask index assignments that synchronise the host; the
 // data is ~50 MB per step at 8 x 512^2, so one coalesced read of each operand is all there is to do here.
+//
+// --balance_Lab (loss.py:484-507) is the same pass with one more operand, the compile-time parameter `Balanced` of the three bodies
+// below: the Lab term of a pixel is weighted by w = S[ka][kb] * m, w = 1 where that is 0, with (ka, kb) the bin of the TARGET pixel's
+// (a, b) (cl_bin), S the [256][256] fp32 table of michigan_hip/losses/lab_balance.h and m the hair plane.  The gather is 4 bytes per
+// pixel from a 256 KiB table that stays in L2.  The unbalanced kernels keep their signatures and their code: their bodies are the
+// Balanced = false instantiation, in which the weight does not exist.
+#include "michigan_hip/losses/lab_balance.h"
 #include "mg_common.h"
 #include "mg_launch.h"
 #include "mg_lab.h"
@@ -24,10 +31,27 @@ namespace {
 
 constexpr int CL_BLOCKS = 1024;                                   // rows of the workspace: ws[term * CL_BLOCKS + block]
 
-template <typename T>
-__global__ __launch_bounds__(256) void color_loss_partial_kernel(const T* __restrict__ img, const float* __restrict__ real, int64_t real_nstride,
-                                                                 const float* __restrict__ back, int64_t back_nstride, int N, int64_t HW, int C,
-                                                                 int flags, float* __restrict__ ws)
+// bin of one Lab coordinate: trunc(clamp(v + 128, 0, 255)) in fp32 (loss.py:496-499); a NaN lands in bin 0, so the index is always in the table
+__device__ __forceinline__ int cl_bin(float v)
+{
+    float t = v + 128.f;
+    t = t > 0.f ? t : 0.f;
+    t = t < 255.f ? t : 255.f;
+    return (int)t;
+}
+
+// the weight of a pixel's Lab term from the target's (a, b): S[ka][kb] * m, and 1 where that is 0 (loss.py:503-505)
+__device__ __forceinline__ float cl_weight(const float* __restrict__ table, float ar, float br, float m)
+{
+    const float w = table[cl_bin(ar) * 256 + cl_bin(br)] * m;
+    return w == 0.f ? 1.f : w;
+}
+
+template <typename T, bool Balanced>
+__device__ __forceinline__ void color_loss_partial_body(const T* __restrict__ img, const float* __restrict__ real, int64_t real_nstride,
+                                                        const float* __restrict__ back, int64_t back_nstride,
+                                                        const float* __restrict__ hair, int64_t hair_nstride, const float* __restrict__ table,
+                                                        int N, int64_t HW, int C, int flags, float* __restrict__ ws)
 {
     __shared__ float red[3][4];
     float s[3] = {0.f, 0.f, 0.f};                                 // lab, rgb, background
@@ -43,7 +67,8 @@ __global__ __launch_bounds__(256) void color_loss_partial_kernel(const T* __rest
             float af, bf, ar, br;
             cl_ab(xf, af, bf);
             cl_ab(xr, ar, br);
-            s[0] += fabsf(af - ar) + fabsf(bf - br);
+            if constexpr (Balanced) s[0] += cl_weight(table, ar, br, hair[(int64_t)n * hair_nstride + pix]) * (fabsf(af - ar) + fabsf(bf - br));
+            else s[0] += fabsf(af - ar) + fabsf(bf - br);
         }
         if (flags & 2) s[1] += fabsf(xf[0] - xr[0]) + fabsf(xf[1] - xr[1]) + fabsf(xf[2] - xr[2]);
         if (flags & 4) {
@@ -53,6 +78,24 @@ __global__ __launch_bounds__(256) void color_loss_partial_kernel(const T* __rest
     }
     const float t = mg_block_sum_to<MgJoin::LeftToRight>(s, red);
     if (threadIdx.x < 3) ws[threadIdx.x * CL_BLOCKS + blockIdx.x] = t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void color_loss_partial_kernel(const T* __restrict__ img, const float* __restrict__ real, int64_t real_nstride,
+                                                                 const float* __restrict__ back, int64_t back_nstride, int N, int64_t HW, int C,
+                                                                 int flags, float* __restrict__ ws)
+{
+    color_loss_partial_body<T, false>(img, real, real_nstride, back, back_nstride, nullptr, 0, nullptr, N, HW, C, flags, ws);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void color_loss_balanced_partial_kernel(const T* __restrict__ img, const float* __restrict__ real, int64_t real_nstride,
+                                                                          const float* __restrict__ back, int64_t back_nstride,
+                                                                          const float* __restrict__ hair, int64_t hair_nstride,
+                                                                          const float* __restrict__ table, int N, int64_t HW, int C, int flags,
+                                                                          float* __restrict__ ws)
+{
+    color_loss_partial_body<T, true>(img, real, real_nstride, back, back_nstride, hair, hair_nstride, table, N, HW, C, flags, ws);
 }
 
 __global__ __launch_bounds__(256) void color_loss_final_kernel(const float* __restrict__ ws, int nblk, double inv_lab, double inv_rgb, float* __restrict__ out)
@@ -69,12 +112,13 @@ __global__ __launch_bounds__(256) void color_loss_final_kernel(const float* __re
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void color_loss_bwd_kernel(const T* __restrict__ img, const float* __restrict__ real, int64_t real_nstride,
-                                                             const float* __restrict__ back, int64_t back_nstride,
-                                                             const float* __restrict__ g_lab, const float* __restrict__ g_rgb,
-                                                             const float* __restrict__ g_back, int N, int64_t HW, int C, int flags,
-                                                             T* __restrict__ dimg)
+template <typename T, bool Balanced>
+__device__ __forceinline__ void color_loss_bwd_body(const T* __restrict__ img, const float* __restrict__ real, int64_t real_nstride,
+                                                    const float* __restrict__ back, int64_t back_nstride,
+                                                    const float* __restrict__ hair, int64_t hair_nstride, const float* __restrict__ table,
+                                                    const float* __restrict__ g_lab, const float* __restrict__ g_rgb,
+                                                    const float* __restrict__ g_back, int N, int64_t HW, int C, int flags,
+                                                    T* __restrict__ dimg)
 {
     const int64_t total = (int64_t)N * HW;
     // d mean / d element, and the /2 of rgb01 for the Lab chain
@@ -92,10 +136,12 @@ __global__ __launch_bounds__(256) void color_loss_bwd_kernel(const T* __restrict
             float xyz[3], ar, br;
             cl_xyz(xf, xyz);
             cl_ab(xr, ar, br);
+            float g = gl;
+            if constexpr (Balanced) g = gl * cl_weight(table, ar, br, hair[(int64_t)n * hair_nstride + pix]);
             const float fx = cl_f(xyz[0]), fy = cl_f(xyz[1]), fz = cl_f(xyz[2]);
             const float sa = 500.f * cl_sign(500.f * (fx - fy) - ar), sb = 200.f * cl_sign(200.f * (fy - fz) - br);
             // dL/dX, dL/dY, dL/dZ, then through the matrix rows
-            const float dX = gl * sa * cl_df(xyz[0]), dY = gl * (sb - sa) * cl_df(xyz[1]), dZ = -gl * sb * cl_df(xyz[2]);
+            const float dX = g * sa * cl_df(xyz[0]), dY = g * (sb - sa) * cl_df(xyz[1]), dZ = -g * sb * cl_df(xyz[2]);
 #pragma unroll
             for (int c = 0; c < 3; ++c) d[c] = dX * cl_m(0, c) + dY * cl_m(1, c) + dZ * cl_m(2, c);
         }
@@ -110,6 +156,28 @@ __global__ __launch_bounds__(256) void color_loss_bwd_kernel(const T* __restrict
         }
         cl_store_rgb_grad(dimg + i * C, C, d);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void color_loss_bwd_kernel(const T* __restrict__ img, const float* __restrict__ real, int64_t real_nstride,
+                                                             const float* __restrict__ back, int64_t back_nstride,
+                                                             const float* __restrict__ g_lab, const float* __restrict__ g_rgb,
+                                                             const float* __restrict__ g_back, int N, int64_t HW, int C, int flags,
+                                                             T* __restrict__ dimg)
+{
+    color_loss_bwd_body<T, false>(img, real, real_nstride, back, back_nstride, nullptr, 0, nullptr, g_lab, g_rgb, g_back, N, HW, C, flags, dimg);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void color_loss_balanced_bwd_kernel(const T* __restrict__ img, const float* __restrict__ real, int64_t real_nstride,
+                                                                      const float* __restrict__ back, int64_t back_nstride,
+                                                                      const float* __restrict__ hair, int64_t hair_nstride,
+                                                                      const float* __restrict__ table,
+                                                                      const float* __restrict__ g_lab, const float* __restrict__ g_rgb,
+                                                                      const float* __restrict__ g_back, int N, int64_t HW, int C, int flags,
+                                                                      T* __restrict__ dimg)
+{
+    color_loss_bwd_body<T, true>(img, real, real_nstride, back, back_nstride, hair, hair_nstride, table, g_lab, g_rgb, g_back, N, HW, C, flags, dimg);
 }
 
 }  // namespace
@@ -150,5 +218,46 @@ extern "C" int mg_color_loss_bwd(const void* img, const float* real, int64_t rea
     mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
         hipLaunchKernelGGL(color_loss_bwd_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)img, real, real_nstride, back, back_nstride, g_lab, g_rgb, g_back, N, HW, C, flags, (T*)dimg); });
     MG_CHECK_LAUNCH("mg_color_loss_bwd");
+    return MG_OK;
+}
+
+// ---- the balanced entry points (michigan_hip/losses/lab_balance.h): the same launches with the hair plane and the table ----------------
+#define MGC_COLOR_CHECK(name) \
+    MG_CHECK_ARG(flags & 1, name ": flags must contain lab (1): the table weights the Lab term"); \
+    MG_COLOR_CHECK(name); \
+    MG_CHECK_ARG(hair && hair_nstride >= (int64_t)H * W, name ": the balanced Lab term needs the hair plane"); \
+    MG_CHECK_ARG(table, name ": null pointer (table)")
+
+extern "C" int mgc_color_loss_balanced_fwd(const void* img, const float* real, int64_t real_nstride, const float* back, int64_t back_nstride,
+                                           const float* hair, int64_t hair_nstride, const float* table,
+                                           int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flags, float* out, float* ws, void* stream)
+{
+    MG_CHECK_ARG(img && real && out && ws, "mgc_color_loss_balanced_fwd: null pointer");
+    MGC_COLOR_CHECK("mgc_color_loss_balanced_fwd");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t HW = (int64_t)H * W;
+    const int grid = mg_ew_grid((int64_t)N * HW, CL_BLOCKS);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(color_loss_balanced_partial_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)img, real, real_nstride, back, back_nstride, hair, hair_nstride, table, N, HW, C, flags, ws); });
+    MG_CHECK_LAUNCH("mgc_color_loss_balanced_fwd");
+    const double cnt = (double)N * (double)HW;
+    hipLaunchKernelGGL(color_loss_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, grid, 1.0 / (2.0 * cnt), 1.0 / (3.0 * cnt), out);
+    MG_CHECK_LAUNCH("mgc_color_loss_balanced_fwd(final)");
+    return MG_OK;
+}
+
+extern "C" int mgc_color_loss_balanced_bwd(const void* img, const float* real, int64_t real_nstride, const float* back, int64_t back_nstride,
+                                           const float* hair, int64_t hair_nstride, const float* table,
+                                           const float* g_lab, const float* g_rgb, const float* g_back,
+                                           int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flags, void* dimg, void* stream)
+{
+    MG_CHECK_ARG(img && real && dimg, "mgc_color_loss_balanced_bwd: null pointer");
+    MGC_COLOR_CHECK("mgc_color_loss_balanced_bwd");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t HW = (int64_t)H * W;
+    const int grid = mg_ew_grid((int64_t)N * HW, 4096);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(color_loss_balanced_bwd_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)img, real, real_nstride, back, back_nstride, hair, hair_nstride, table, g_lab, g_rgb, g_back, N, HW, C, flags, (T*)dimg); });
+    MG_CHECK_LAUNCH("mgc_color_loss_balanced_bwd");
     return MG_OK;
 }

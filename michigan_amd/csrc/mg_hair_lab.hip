@@ -12,6 +12,13 @@
 //   hair_lab_bwd_kernel       dimg in the image's dtype and layout, padding channels zero; reads `stats`, reduces nothing
 // What is provably zero is not read: img only where m_f != 0 (bit 0) or m_b != 0 (bit 1), ref only where m_r != 0, tgt only where
 // m_b != 0 -- with a one-hot label every pixel takes exactly one of the two branches.
+//
+// --balance_Lab (loss.py:578-600, 614-618) changes the per-sample tail alone: the final kernel looks the sample's weight w_n up in the
+// [256][256] fp32 table of michigan_hip/losses/lab_balance.h at the bin of the REFERENCE image's mean hair colour (the mean rounded to
+// fp32, + 128.f, clamped, truncated; no zero-to-one replacement, so a zero of the table gives weight 0), sums w_n (|da_n| + |db_n|)
+// and leaves w_n in a `stats` row of MGC_HAIR_STATS floats; the backward multiplies its per-sample scale by it.  `Balanced` is a
+// compile-time parameter of the two bodies; the unbalanced kernels keep their signatures and their code.
+#include "michigan_hip/losses/lab_balance.h"
 #include "mg_common.h"
 #include "mg_launch.h"
 #include "mg_lab.h"
@@ -69,9 +76,19 @@ __global__ __launch_bounds__(256) void hair_lab_partial_kernel(const T* __restri
     if (threadIdx.x < HL_TERMS) ws[((int64_t)threadIdx.x * N + n) * gridDim.x + blockIdx.x] = t;
 }
 
+// bin of one mean Lab coordinate: the double mean rounded to fp32, then trunc(clamp(v + 128, 0, 255)) in fp32 (loss.py:590-594)
+__device__ __forceinline__ int hl_bin(double mean)
+{
+    float t = (float)mean + 128.f;
+    t = t > 0.f ? t : 0.f;
+    t = t < 255.f ? t : 255.f;
+    return (int)t;
+}
+
 // one workgroup; wave w owns samples w, w + 4, ...: lanes stride over the sample's partials, a fixed shuffle tree joins them
-__global__ __launch_bounds__(256) void hair_lab_final_kernel(const float* __restrict__ ws, int N, int bps, int flags, double inv_hair, double inv_back,
-                                                             float* __restrict__ stats, float* __restrict__ out)
+template <bool Balanced>
+__device__ __forceinline__ void hair_lab_final_body(const float* __restrict__ ws, const float* __restrict__ table, int N, int bps, int flags,
+                                                    double inv_hair, double inv_back, float* __restrict__ stats, float* __restrict__ out)
 {
     __shared__ double red[2][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -88,9 +105,17 @@ __global__ __launch_bounds__(256) void hair_lab_final_kernel(const float* __rest
             if (flags & 1) {
                 const double sf = s[0] == 0.0 ? 1.0 : s[0], sr = s[3] == 0.0 ? 1.0 : s[3];      // mask_sum[mask_sum == 0] = 1 (loss.py:575)
                 const double da = s[1] / sf - s[4] / sr, db = s[2] / sf - s[5] / sr;
-                hair += fabs(da) + fabs(db);
                 const f32x4_t v = {(float)da, (float)db, (float)(1.0 / sf), (float)(1.0 / sr)};
-                ET<float>::store4(stats + 4 * (int64_t)n, v);
+                if constexpr (Balanced) {
+                    const float w = table[hl_bin(s[4] / sr) * 256 + hl_bin(s[5] / sr)];
+                    hair += (double)w * (fabs(da) + fabs(db));
+                    const f32x4_t v1 = {w, 0.f, 0.f, 0.f};
+                    ET<float>::store4(stats + MGC_HAIR_STATS * (int64_t)n, v);
+                    ET<float>::store4(stats + MGC_HAIR_STATS * (int64_t)n + 4, v1);
+                } else {
+                    hair += fabs(da) + fabs(db);
+                    ET<float>::store4(stats + 4 * (int64_t)n, v);
+                }
             }
             bg += s[6];
         }
@@ -103,22 +128,36 @@ __global__ __launch_bounds__(256) void hair_lab_final_kernel(const float* __rest
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void hair_lab_bwd_kernel(const T* __restrict__ img, const float* __restrict__ mf, int64_t mf_nstride,
-                                                           const float* __restrict__ tgt, int64_t tgt_nstride,
-                                                           const float* __restrict__ back, int64_t back_nstride,
-                                                           const float* __restrict__ stats, const float* __restrict__ g_hair,
-                                                           const float* __restrict__ g_back, int N, int64_t HW, int C, int flags,
-                                                           T* __restrict__ dimg)
+__global__ __launch_bounds__(256) void hair_lab_final_kernel(const float* __restrict__ ws, int N, int bps, int flags, double inv_hair, double inv_back,
+                                                             float* __restrict__ stats, float* __restrict__ out)
+{
+    hair_lab_final_body<false>(ws, nullptr, N, bps, flags, inv_hair, inv_back, stats, out);
+}
+
+__global__ __launch_bounds__(256) void hair_lab_balanced_final_kernel(const float* __restrict__ ws, const float* __restrict__ table, int N, int bps,
+                                                                      int flags, double inv_hair, double inv_back, float* __restrict__ stats,
+                                                                      float* __restrict__ out)
+{
+    hair_lab_final_body<true>(ws, table, N, bps, flags, inv_hair, inv_back, stats, out);
+}
+
+template <typename T, bool Balanced>
+__device__ __forceinline__ void hair_lab_bwd_body(const T* __restrict__ img, const float* __restrict__ mf, int64_t mf_nstride,
+                                                  const float* __restrict__ tgt, int64_t tgt_nstride,
+                                                  const float* __restrict__ back, int64_t back_nstride,
+                                                  const float* __restrict__ stats, const float* __restrict__ g_hair,
+                                                  const float* __restrict__ g_back, int N, int64_t HW, int C, int flags,
+                                                  T* __restrict__ dimg)
 {
     const int n = blockIdx.y;
     const bool hair = (flags & 1) && g_hair, bgt = (flags & 2) && g_back;
     float sa = 0.f, sb = 0.f, gl = 0.f;
     if (hair) {
-        const f32x4_t st = ET<float>::load4(stats + 4 * (int64_t)n);
+        const f32x4_t st = ET<float>::load4(stats + (Balanced ? MGC_HAIR_STATS : 4) * (int64_t)n);
         sa = 500.f * cl_sign(st[0]);
         sb = 200.f * cl_sign(st[1]);
         gl = g_hair[0] * (float)(0.5 / (2.0 * (double)N)) * st[2];    // d mean / d element, the /2 of rgb01, 1 / S_f
+        if constexpr (Balanced) gl = gl * stats[MGC_HAIR_STATS * (int64_t)n + 4];           // ... and the sample's weight
     }
     const float gb = bgt ? g_back[0] * (float)(1.0 / (3.0 * (double)N * (double)HW)) : 0.f;
     const T* __restrict__ ip = img + (int64_t)n * HW * C;
@@ -145,6 +184,28 @@ __global__ __launch_bounds__(256) void hair_lab_bwd_kernel(const T* __restrict__
         }
         cl_store_rgb_grad(op + pix * C, C, d);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void hair_lab_bwd_kernel(const T* __restrict__ img, const float* __restrict__ mf, int64_t mf_nstride,
+                                                           const float* __restrict__ tgt, int64_t tgt_nstride,
+                                                           const float* __restrict__ back, int64_t back_nstride,
+                                                           const float* __restrict__ stats, const float* __restrict__ g_hair,
+                                                           const float* __restrict__ g_back, int N, int64_t HW, int C, int flags,
+                                                           T* __restrict__ dimg)
+{
+    hair_lab_bwd_body<T, false>(img, mf, mf_nstride, tgt, tgt_nstride, back, back_nstride, stats, g_hair, g_back, N, HW, C, flags, dimg);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void hair_lab_balanced_bwd_kernel(const T* __restrict__ img, const float* __restrict__ mf, int64_t mf_nstride,
+                                                                    const float* __restrict__ tgt, int64_t tgt_nstride,
+                                                                    const float* __restrict__ back, int64_t back_nstride,
+                                                                    const float* __restrict__ stats, const float* __restrict__ g_hair,
+                                                                    const float* __restrict__ g_back, int N, int64_t HW, int C, int flags,
+                                                                    T* __restrict__ dimg)
+{
+    hair_lab_bwd_body<T, true>(img, mf, mf_nstride, tgt, tgt_nstride, back, back_nstride, stats, g_hair, g_back, N, HW, C, flags, dimg);
 }
 
 }  // namespace
@@ -193,5 +254,47 @@ extern "C" int mg_hair_lab_bwd(const void* img, const float* hair_tag, int64_t h
     mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
         hipLaunchKernelGGL(hair_lab_bwd_kernel<T>, grid, dim3(256), 0, st, (const T*)img, hair_tag, hair_tag_nstride, tgt, tgt_nstride, back, back_nstride, stats, g_hair, g_back, N, HW, C, flags, (T*)dimg); });
     MG_CHECK_LAUNCH("mg_hair_lab_bwd");
+    return MG_OK;
+}
+
+// ---- the balanced entry points (michigan_hip/losses/lab_balance.h): the same partial pass, the weighted tail -----------------------------
+#define MGC_HAIR_CHECK(name) \
+    MG_CHECK_ARG(flags & 1, name ": flags must contain hairAvgLab (1): the table weights that term"); \
+    MG_HAIR_CHECK(name); \
+    MG_CHECK_ARG(stats, name ": null pointer (stats)")
+
+extern "C" int mgc_hair_lab_balanced_fwd(const void* img, const float* ref, int64_t ref_nstride, const float* hair_tag, int64_t hair_tag_nstride,
+                                         const float* hair_ref, int64_t hair_ref_nstride, const float* tgt, int64_t tgt_nstride,
+                                         const float* back, int64_t back_nstride, const float* table, int32_t dtype, int32_t N, int32_t H, int32_t W,
+                                         int32_t C, int32_t flags, float* out, float* stats, float* ws, void* stream)
+{
+    MG_CHECK_ARG(img && out && ws && table, "mgc_hair_lab_balanced_fwd: null pointer");
+    MGC_HAIR_CHECK("mgc_hair_lab_balanced_fwd");
+    MG_CHECK_ARG(ref && ref_nstride >= 3 * (int64_t)H * W, "mgc_hair_lab_balanced_fwd: the hairAvgLab term needs three dense planes per sample of the reference image");
+    MG_CHECK_ARG(hair_ref && hair_ref_nstride >= (int64_t)H * W, "mgc_hair_lab_balanced_fwd: the hairAvgLab term needs the reference hair plane");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t HW = (int64_t)H * W;
+    const int bps = hl_bps(HW, N, HL_BLOCKS);
+    const dim3 grid(bps, N);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(hair_lab_partial_kernel<T>, grid, dim3(256), 0, st, (const T*)img, ref, ref_nstride, hair_tag, hair_tag_nstride, hair_ref, hair_ref_nstride, tgt, tgt_nstride, back, back_nstride, N, HW, C, flags, ws); });
+    MG_CHECK_LAUNCH("mgc_hair_lab_balanced_fwd");
+    hipLaunchKernelGGL(hair_lab_balanced_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, table, N, bps, flags, 1.0 / (2.0 * (double)N), 1.0 / (3.0 * (double)N * (double)HW), stats, out);
+    MG_CHECK_LAUNCH("mgc_hair_lab_balanced_fwd(final)");
+    return MG_OK;
+}
+
+extern "C" int mgc_hair_lab_balanced_bwd(const void* img, const float* hair_tag, int64_t hair_tag_nstride, const float* tgt, int64_t tgt_nstride,
+                                         const float* back, int64_t back_nstride, const float* stats, const float* g_hair, const float* g_back,
+                                         int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flags, void* dimg, void* stream)
+{
+    MG_CHECK_ARG(img && dimg, "mgc_hair_lab_balanced_bwd: null pointer");
+    MGC_HAIR_CHECK("mgc_hair_lab_balanced_bwd");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t HW = (int64_t)H * W;
+    const dim3 grid(hl_bps(HW, N, 4096), N);
+    mg_by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(hair_lab_balanced_bwd_kernel<T>, grid, dim3(256), 0, st, (const T*)img, hair_tag, hair_tag_nstride, tgt, tgt_nstride, back, back_nstride, stats, g_hair, g_back, N, HW, C, flags, (T*)dimg); });
+    MG_CHECK_LAUNCH("mgc_hair_lab_balanced_bwd");
     return MG_OK;
 }

@@ -13,8 +13,9 @@ is a second network `netD2` with its own Adam (pix2pix_model.py:147-150,568-572,
 objective is GAN + ORIENT (+ CONFIDENCE) + hairAvgLab + background (pix2pix_model.py:352-363), the last two as one fused
 pass (mg_hair_lab_*).  The style / content terms (pix2pix_model.py:309-319, on by default in the reference, switched off by the
 README command and by `default_options()`) are fused feature-moment passes over the VGG taps (mg_feat_moment_loss_*), computed at
-`curr_step == 1` whether or not the reference is the target, on the tower pass the VGG loss already pays for.  balance_Lab and the
-blender are outside this tier's scope.  Mode 'demo_inference' (pix2pix_model.py:94-120) is the interactive demo's call:
+`curr_step == 1` whether or not the reference is the target, on the tower pass the VGG loss already pays for.  Under `balance_Lab`
+(`weight_dir`, `Lab_weight_th`) the Lab term of the fused colour pass and the hair-average Lab term take the histogram weighting from ONE
+table (networks.LabBalance), as one more operand of the same passes.  The blender is outside this tier's scope.  Mode 'demo_inference' (pix2pix_model.py:94-120) is the interactive demo's call:
 with `use_stroke` a second frozen net (netSIG) fills the hole around the user's strokes (`inpainting_stroke_orient`), and the call returns the
 generated image and the in-painted orientation picture.
 
@@ -76,7 +77,9 @@ def default_options(**over) -> argparse.Namespace:
         # image-space L1 terms (pix2pix_model.py:317-336).  The README recipe is no_lab_loss=False (lambda_lab 1); all three stay off
         # here so that the recorded fixtures and benchmark numbers keep their objective -- switch them on per run
         no_lab_loss=True, no_rgb_loss=True, no_background_loss=True, lambda_lab=1.0, lambda_rgb=1.0, lambda_background=1.0,
-        balance_Lab=False,
+        # --balance_Lab (loss.py:484-507, 578-600): weight_dir names the histogram of hair colours (the reference's data/ab_count.npy;
+        # this package ships none), Lab_weight_th caps the weights
+        balance_Lab=False, weight_dir=None, Lab_weight_th=10.0,
         # style / content (pix2pix_model.py:309-319; on by default in the reference, off in the README command): off here for the same
         # reason as the colour terms
         no_style_loss=True, no_content_loss=True, lambda_style=1.0, lambda_content=1.0,
@@ -106,10 +109,11 @@ class Pix2PixModel(nn.Module):
                     self.criterionVGG.vgg.compute_dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}.get(dt, dt)
             if not getattr(opt, "no_orient_loss", True):
                 self.criterionOrient = networks.L1OLoss(opt)
-            if not getattr(opt, "no_lab_loss", True) and getattr(opt, "balance_Lab", False):
-                raise NotImplementedError("Lab colour loss: the balance_Lab weighting is not implemented")
+            self.lab_balance = None                              # ONE weight table for the Lab term and the hair-average Lab term
+            if getattr(opt, "balance_Lab", False) and (not getattr(opt, "no_lab_loss", True) or getattr(opt, "unpairTrain", False)):
+                self.lab_balance = networks.LabBalance(opt)      # NotImplementedError without opt.weight_dir
             if getattr(opt, "unpairTrain", False):
-                self.criterionHairAvgLab = networks.HairAvgLabLoss(opt)
+                self.criterionHairAvgLab = networks.HairAvgLabLoss(opt, balance=self.lab_balance)
             if not (getattr(opt, "no_style_loss", True) and getattr(opt, "no_content_loss", True)):
                 shared = self.criterionVGG.vgg if not opt.no_vgg_loss else None
                 self.criterionStyleContent = networks.StyleContentLoss(opt, vgg=shared)
@@ -421,7 +425,10 @@ class Pix2PixModel(nn.Module):
                      | (0 if getattr(self.opt, "no_rgb_loss", True) else ops.COLOR_RGB)
                      | (0 if getattr(self.opt, "no_background_loss", True) else ops.COLOR_BACKGROUND))
             if flags:
-                lab, rgb, back = ops.color_losses(fake.permute(0, 2, 3, 1), d["image_tag"], d["input_tag"].detach()[:, 0], flags)
+                balanced = self.lab_balance is not None and bool(flags & ops.COLOR_LAB)
+                lab, rgb, back = ops.color_losses(fake.permute(0, 2, 3, 1), d["image_tag"], d["input_tag"].detach()[:, 0], flags,
+                                                  hair=d["input_tag"].detach()[:, 1] if balanced else None,
+                                                  table=self.lab_balance.table(fake.device) if balanced else None)
                 if flags & ops.COLOR_BACKGROUND:
                     losses["background"] = _scaled(back, getattr(self.opt, "lambda_background", 1.0))
                 if flags & ops.COLOR_RGB:
@@ -431,7 +438,8 @@ class Pix2PixModel(nn.Module):
         if self._unpaired_step():
             # hairAvgLab + background (pix2pix_model.py:352-363; background regardless of no_background_loss there): ONE pass over fake
             hair, back = ops.hair_lab_losses(fake.permute(0, 2, 3, 1), d["image_ref"], d["input_tag"].detach()[:, 1], d["input_ref"].detach()[:, 1],
-                                             d["image_tag"], d["input_tag"].detach()[:, 0], ops.HAIR_LAB | ops.HAIR_BACKGROUND)
+                                             d["image_tag"], d["input_tag"].detach()[:, 0], ops.HAIR_LAB | ops.HAIR_BACKGROUND,
+                                             table=self.lab_balance.table(fake.device) if self.lab_balance is not None else None)
             losses["hairAvgLab"] = _scaled(hair, getattr(self.opt, "lambda_hairavglab", 1.0))
             losses["background"] = _scaled(back, getattr(self.opt, "lambda_background", 1.0))
         if branch:

@@ -18,14 +18,14 @@ from .discriminator import MultiscaleDiscriminator, NLayerDiscriminator
 from .encoder import BackgroundEncode2, ConvBlock, ImageEncoder3, PartialConv2d
 from .generator import SPADEBGenerator
 from .inpaint import InpaintGenerator, SInpaintGenerator
-from .loss import GANFeatLoss, GANLoss, HairAvgLabLoss, L1OLoss, LabColorLoss, RGBBackgroundL1Loss, StyleContentLoss, VGGLoss
+from .loss import GANFeatLoss, GANLoss, HairAvgLabLoss, L1OLoss, LabBalance, LabColorLoss, RGBBackgroundL1Loss, StyleContentLoss, VGGLoss
 from .normalization import SPADE, SegPyramid, get_nonspade_norm_layer
 from .sync_batchnorm import DataParallelWithCallback, SynchronizedBatchNorm2d
 
 __all__ = [
     "BaseNetwork", "SPADEBGenerator", "MultiscaleDiscriminator", "NLayerDiscriminator", "SPADEResnetBlock",
     "SPADE", "SegPyramid", "VGG19", "ImageEncoder3", "BackgroundEncode2", "PartialConv2d", "ConvBlock",
-    "GANLoss", "GANFeatLoss", "VGGLoss", "L1OLoss", "LabColorLoss", "RGBBackgroundL1Loss", "HairAvgLabLoss", "StyleContentLoss", "SynchronizedBatchNorm2d", "DataParallelWithCallback",
+    "GANLoss", "GANFeatLoss", "VGGLoss", "L1OLoss", "LabColorLoss", "LabBalance", "RGBBackgroundL1Loss", "HairAvgLabLoss", "StyleContentLoss", "SynchronizedBatchNorm2d", "DataParallelWithCallback",
     "get_nonspade_norm_layer", "find_network_using_name", "modify_commandline_options", "create_network",
     "define_G", "define_D", "define_IG", "define_SIG", "InpaintGenerator", "SInpaintGenerator",
 ]

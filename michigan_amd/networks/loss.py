@@ -4,8 +4,9 @@ Reductions run in fp32 on whatever dtype the discriminator / VGG towers produced
 loss with its wide-edge weight mask (mg_hinge_*, mg_wide_edge_weight), discriminator feature matching and the VGG taps
 (mg_l1_mean_*), the orientation loss under either filter bank (mg_gabor_argmax_*, then mg_orient_loss_* / mgl_orient_dog_*), and the image-space Lab colour / background / RGB L1
 terms as one pass (mg_color_loss_*), the unpaired stage's hair-average Lab term (mg_hair_lab_*, fused with the background
-term in the model), and the style / content terms as fused feature-moment passes over the VGG taps (mg_feat_moment_loss_*).  The
-balance_Lab weighting is out of scope; under michigan_amd.dropin style / content stay the reference's own class."""
+term in the model), and the style / content terms as fused feature-moment passes over the VGG taps (mg_feat_moment_loss_*).  Under
+--balance_Lab the two Lab terms take the histogram weighting as one more operand of the same passes (mgc_*_balanced_*, LabBalance).
+Under michigan_amd.dropin style / content stay the reference's own class."""
 from __future__ import annotations
 
 import math
@@ -241,34 +242,73 @@ class RGBBackgroundL1Loss(nn.Module):
         return ops.color_losses(_image_nhwc(fake), image_tag, input_semantics.detach()[:, 0], ops.COLOR_BACKGROUND)[2]
 
 
-class LabColorLoss(nn.Module):
-    """L1 between the a and b channels of the generated and the target image in CIE Lab (reference: loss.py:403-532,
-    the rgb2xyz / xyz2lab route; L is not part of the loss).  `opt.balance_Lab` (a histogram-weighted variant that
-    needs `opt.weight_dir`) is not implemented."""
+class LabBalance:
+    """The weight table of --balance_Lab (cal_weight, loss.py:484-507 and 578-600): the histogram of hair colours over the a/b plane that
+    `opt.weight_dir` names (the reference's data/ab_count.npy, 256 x 256 counts) is loaded ONCE, here -- the reference reloads it on every
+    call -- and turned into the fp32 table by ops.lab_weight_table with the cap `opt.Lab_weight_th` (default 10) on the device of the
+    first call.  One instance may serve both Lab criteria."""
 
     def __init__(self, opt):
+        import numpy as np
+        path = getattr(opt, "weight_dir", None)
+        if not path:
+            raise NotImplementedError("balance_Lab: this package ships no histogram of hair colours: --weight_dir (the reference's "
+                                      "data/ab_count.npy; an .npz archive of that one array is taken as well) is required")
+        raw = np.load(path)
+        if hasattr(raw, "files"):                                 # an .npz archive with one array
+            raw = raw[raw.files[0]]
+        self.th = float(getattr(opt, "Lab_weight_th", 10.0))
+        self.host = ops.lab_weight_table(raw, self.th)
+        self._tables = {}
+
+    @classmethod
+    def of(cls, opt, shared=None):
+        """`shared` if given, a new table under opt.balance_Lab, else None."""
+        if shared is not None:
+            return shared
+        return cls(opt) if getattr(opt, "balance_Lab", False) else None
+
+    def table(self, device):
+        device = torch.device(device)
+        t = self._tables.get(device)
+        if t is None:
+            t = self._tables[device] = self.host.to(device)
+        return t
+
+
+class LabColorLoss(nn.Module):
+    """L1 between the a and b channels of the generated and the target image in CIE Lab (reference: loss.py:403-532,
+    the rgb2xyz / xyz2lab route; L is not part of the loss).  Under `opt.balance_Lab` a pixel's term is weighted by the table entry of
+    the target pixel's colour times `mask` (the hair plane [N, 1, H, W]; its value multiplies), 1 where that is 0 (LabBalance;
+    `balance`: an instance to share)."""
+
+    def __init__(self, opt, balance=None):
         super().__init__()
-        if getattr(opt, "balance_Lab", False):
-            raise NotImplementedError("Lab colour loss: the balance_Lab weighting is not implemented")
+        self.balance = LabBalance.of(opt, balance)
         self.opt = opt
 
     def forward(self, fake, real, mask=None):
-        return ops.color_losses(_image_nhwc(fake), real, None, ops.COLOR_LAB)[0]
+        if self.balance is None:
+            return ops.color_losses(_image_nhwc(fake), real, None, ops.COLOR_LAB)[0]
+        if mask is None:
+            raise ValueError("LabColorLoss: under balance_Lab the hair mask [N, 1, H, W] is needed")
+        return ops.color_losses(_image_nhwc(fake), real, None, ops.COLOR_LAB, hair=mask.detach()[:, 0], table=self.balance.table(fake.device))[0]
 
 
 class HairAvgLabLoss(nn.Module):
     """L1 between the mean Lab (a, b) colour of the generated hair inside `mask_fake` and of the reference image's hair inside
     `mask_real`, one pair of means per sample (reference: loss.py:534-621; masks [N, 1, H, W], their values multiply; an empty
-    mask divides by 1).  `opt.balance_Lab` (needs `opt.weight_dir` and a grid_sample whose default changed) is not implemented."""
+    mask divides by 1).  Under `opt.balance_Lab` sample n's term is weighted by the table entry of the reference's mean hair colour
+    (LabBalance; `balance`: an instance to share); a zero of the table is a weight of 0 here."""
 
-    def __init__(self, opt):
+    def __init__(self, opt, balance=None):
         super().__init__()
-        if getattr(opt, "balance_Lab", False):
-            raise NotImplementedError("hair-average Lab loss: the balance_Lab weighting is not implemented")
+        self.balance = LabBalance.of(opt, balance)
         self.opt = opt
 
     def forward(self, fake, real, mask_fake, mask_real):
-        return ops.hair_lab_losses(_image_nhwc(fake), real, mask_fake.detach()[:, 0], mask_real.detach()[:, 0], flags=ops.HAIR_LAB)[0]
+        table = self.balance.table(fake.device) if self.balance is not None else None
+        return ops.hair_lab_losses(_image_nhwc(fake), real, mask_fake.detach()[:, 0], mask_real.detach()[:, 0], flags=ops.HAIR_LAB, table=table)[0]
 
 
 class StyleContentLoss(nn.Module):

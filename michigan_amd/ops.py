@@ -20,6 +20,7 @@ Reference call sites replaced (all ATen today):
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import weakref
 from typing import List, Optional, Sequence, Tuple
@@ -1894,42 +1895,97 @@ def orient_loss_dog(conf_raw: torch.Tensor, idx: torch.Tensor, label: torch.Tens
 
 
 COLOR_LAB, COLOR_RGB, COLOR_BACKGROUND = 1, 2, 4      # `flags` bits of mg_color_loss_*
+LAB_TABLE_BINS, HAIR_LAB_BALANCED_STATS = 256, 8      # MGC_TABLE_BINS, MGC_HAIR_STATS (include/michigan_hip/losses/lab_balance.h)
+
+
+def lab_weight_table(counts, th: float = 10.0, device=None) -> torch.Tensor:
+    """The weight table S of --balance_Lab, fp32 [256, 256] (rows index a, columns index b), from the histogram of hair colours over the
+    a/b plane that `--weight_dir` names (cal_weight, loss.py:486-492): the counts are cast to fp32 FIRST, then in fp32 zeros become 1,
+    w = max(w) / w and w = min(w, th).  Row 255 and column 255 are 0: the reference samples its weights with grid_sample(mode='nearest')
+    under today's default align_corners=False, which maps bin 255 to position 255.5, rounds to 256 and reads the zero padding (the torch
+    the reference was written for, align_corners=True, read w[255][..] there; this package follows the reference as it runs today).
+    Refuses a shape other than 256 x 256, non-finite or negative counts and th <= 0."""
+    import numpy as np
+    c = counts.detach().cpu() if torch.is_tensor(counts) else torch.from_numpy(np.ascontiguousarray(counts))
+    if tuple(c.shape) != (LAB_TABLE_BINS, LAB_TABLE_BINS):
+        raise ValueError(f"lab_weight_table: the histogram has to be 256 x 256, got {tuple(c.shape)}")
+    if c.dtype == torch.bool or c.is_complex():
+        raise ValueError("lab_weight_table: the histogram has to hold counts")
+    th = float(th)
+    if not (th > 0 and math.isfinite(th)):
+        raise ValueError(f"lab_weight_table: the cap Lab_weight_th has to be positive and finite, got {th}")
+    w = c.to(torch.float32)
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError("lab_weight_table: the counts have to be finite and not negative")
+    w[w == 0] = 1
+    w = w.max() / w
+    w[w > th] = th
+    w[LAB_TABLE_BINS - 1, :] = 0
+    w[:, LAB_TABLE_BINS - 1] = 0
+    w = w.contiguous()
+    return w.to(device) if device is not None else w
+
+
+def _lab_table(table: torch.Tensor, who: str, like: torch.Tensor) -> torch.Tensor:
+    """The operand check of a weight table: fp32 [256, 256], dense, on the image's device; any VALUES (the kernels read what is there)."""
+    if not torch.is_tensor(table) or table.dtype != torch.float32 or tuple(table.shape) != (LAB_TABLE_BINS, LAB_TABLE_BINS):
+        raise ValueError(f"{who}: the weight table has to be an fp32 [256, 256] tensor (ops.lab_weight_table)")
+    if table.device != like.device:
+        raise ValueError(f"{who}: the weight table is on {table.device}, the image on {like.device}")
+    return table.detach().contiguous()
 
 
 class _ColorLossFn(torch.autograd.Function):
+    """table None: mg_color_loss_*; a table: mgc_color_loss_balanced_* with (hair, table) behind the background plane."""
+
     @staticmethod
-    def forward(ctx, img, real, back, flags):
+    def forward(ctx, img, real, back, flags, hair=None, table=None):
         img = _nhwc(img)
         n, h, w, c = img.shape
         out = torch.empty(COLOR_LOSS_TERMS, dtype=torch.float32, device=img.device)
         ws = torch.empty(COLOR_LOSS_TERMS * COLOR_LOSS_BLOCKS, dtype=torch.float32, device=img.device)
         bp, bs = _plane_args(back)
-        C.backend().mg_color_loss_fwd(_p(img), _p(real), real.stride(0), bp, bs, _dt(img), n, h, w, c, flags, _p(out), _p(ws), _stream(img))
-        ctx.save_for_backward(img, real, back)
+        if table is None:
+            C.backend().mg_color_loss_fwd(_p(img), _p(real), real.stride(0), bp, bs, _dt(img), n, h, w, c, flags, _p(out), _p(ws), _stream(img))
+        else:
+            hp, hs = _plane_args(hair)
+            C.backend().mgc_color_loss_balanced_fwd(_p(img), _p(real), real.stride(0), bp, bs, hp, hs, _p(table), _dt(img), n, h, w, c, flags,
+                                                    _p(out), _p(ws), _stream(img))
+        ctx.save_for_backward(img, real, back, hair, table)
         ctx.flags = flags
         ctx.set_materialize_grads(False)
         return out[0], out[1], out[2]
 
     @staticmethod
     def backward(ctx, g_lab, g_rgb, g_back):
-        img, real, back = ctx.saved_tensors
+        img, real, back, hair, table = ctx.saved_tensors
         if g_lab is None and g_rgb is None and g_back is None:
-            return None, None, None, None
+            return (None,) * 6
         n, h, w, c = img.shape
         g_lab, g_rgb, g_back = _f32_grads(g_lab, g_rgb, g_back)
         bp, bs = _plane_args(back)
         d = torch.empty_like(img)
-        C.backend().mg_color_loss_bwd(_p(img), _p(real), real.stride(0), bp, bs, _p(g_lab), _p(g_rgb), _p(g_back), _dt(img), n, h, w, c,
-                                      ctx.flags, _p(d), _stream(img))
-        return d, None, None, None
+        if table is None:
+            C.backend().mg_color_loss_bwd(_p(img), _p(real), real.stride(0), bp, bs, _p(g_lab), _p(g_rgb), _p(g_back), _dt(img), n, h, w, c,
+                                          ctx.flags, _p(d), _stream(img))
+        else:
+            hp, hs = _plane_args(hair)
+            C.backend().mgc_color_loss_balanced_bwd(_p(img), _p(real), real.stride(0), bp, bs, hp, hs, _p(table), _p(g_lab), _p(g_rgb), _p(g_back),
+                                                    _dt(img), n, h, w, c, ctx.flags, _p(d), _stream(img))
+        return (d,) + (None,) * 5
 
 
-def color_losses(fake: torch.Tensor, real: torch.Tensor, back: Optional[torch.Tensor], flags: int):
-    """(lab, rgb, background) of the generator objective (LabColorLoss loss.py:403-532 without balance_Lab, nn.L1Loss, RGBBackgroundL1Loss
+def color_losses(fake: torch.Tensor, real: torch.Tensor, back: Optional[torch.Tensor], flags: int, hair: Optional[torch.Tensor] = None,
+                 table: Optional[torch.Tensor] = None):
+    """(lab, rgb, background) of the generator objective (LabColorLoss loss.py:403-532, nn.L1Loss, RGBBackgroundL1Loss
     loss.py:388-400) in one pass: fake NHWC [N, H, W, C >= 3] bf16 / fp32 with RGB in channels 0..2 (`net_output.permute(0, 2, 3, 1)` is
     zero-copy), real NCHW [N, 3, H, W], back fp32 [N, H, W] view (channel 0 of the one-hot label; None unless COLOR_BACKGROUND is set).
     `flags`: COLOR_LAB | COLOR_RGB | COLOR_BACKGROUND; a term not selected is 0 and costs nothing.  Three fp32 scalars (views of one
-    tensor), gradient to `fake` only.  Two launches forward, one backward."""
+    tensor), gradient to `fake` only.  Two launches forward, one backward.
+    `table` (lab_weight_table; any fp32 [256, 256] is read as it stands) selects the --balance_Lab weighting of the Lab term: a pixel's
+    |da| + |db| counts w = table[bin a][bin b] * hair times, once where that is 0, with the bins taken of the TARGET pixel's colour and
+    `hair` the fp32 [N, H, W] view whose value multiplies (channel 1 of the one-hot label).  It needs `hair` and COLOR_LAB; the other two
+    terms ride along unchanged, the launches stay two and one.  Without a table the call is the unbalanced one, launch for launch."""
     flags = int(flags)
     if not 1 <= flags <= 7:
         raise ValueError("color_losses: flags must select at least one of COLOR_LAB, COLOR_RGB, COLOR_BACKGROUND")
@@ -1937,26 +1993,42 @@ def color_losses(fake: torch.Tensor, real: torch.Tensor, back: Optional[torch.Te
             (fake.shape[0], fake.shape[1], fake.shape[2]) != (real.shape[0], real.shape[2], real.shape[3]):
         raise ValueError(f"color_losses: NHWC image {tuple(fake.shape)} does not match the NCHW target {tuple(real.shape)}")
     back = _f32_plane(back, "color_losses: the background plane", fake.shape[:3]) if flags & COLOR_BACKGROUND else None
-    return _ColorLossFn.apply(fake, _f32_dense(real), back, flags)
+    if table is None:
+        if hair is not None:
+            raise ValueError("color_losses: a hair plane without a weight table: the unbalanced Lab term does not read one")
+        return _ColorLossFn.apply(fake, _f32_dense(real), back, flags, None, None)
+    if not flags & COLOR_LAB:
+        raise ValueError("color_losses: a weight table needs COLOR_LAB: it weights the Lab term")
+    table = _lab_table(table, "color_losses", fake)
+    hair = _f32_plane(hair, "color_losses: the hair plane", fake.shape[:3])
+    return _ColorLossFn.apply(fake, _f32_dense(real), back, flags, hair, table)
 
 
 HAIR_LAB, HAIR_BACKGROUND = 1, 2                      # `flags` bits of mg_hair_lab_*
 
 
 class _HairLabLossFn(torch.autograd.Function):
+    """table None: mg_hair_lab_*; a table: mgc_hair_lab_balanced_* (the table behind the background plane, a wider `stats` row)."""
+
     @staticmethod
-    def forward(ctx, img, ref, hair_tag, hair_ref, tgt, back, flags):
+    def forward(ctx, img, ref, hair_tag, hair_ref, tgt, back, flags, table=None):
         img = _nhwc(img)
         n, h, w, c = img.shape
         out = torch.empty(2, dtype=torch.float32, device=img.device)
-        stats = torch.empty(4 * n, dtype=torch.float32, device=img.device) if flags & HAIR_LAB else None
+        row = 4 if table is None else HAIR_LAB_BALANCED_STATS
+        stats = torch.empty(row * n, dtype=torch.float32, device=img.device) if flags & HAIR_LAB else None
         ws = torch.empty(HAIR_LAB_TERMS * max(HAIR_LAB_BLOCKS, n), dtype=torch.float32, device=img.device)
         (fp, fs), (rp, rs), (bp, bs) = _plane_args(hair_tag), _plane_args(hair_ref), _plane_args(back)
-        C.backend().mg_hair_lab_fwd(_p(img), _p(ref), ref.stride(0) if ref is not None else 0, fp, fs, rp, rs,
-                                    _p(tgt), tgt.stride(0) if tgt is not None else 0, bp, bs, _dt(img), n, h, w, c, flags,
-                                    _p(out), _p(stats), _p(ws), _stream(img))
+        if table is None:
+            C.backend().mg_hair_lab_fwd(_p(img), _p(ref), ref.stride(0) if ref is not None else 0, fp, fs, rp, rs,
+                                        _p(tgt), tgt.stride(0) if tgt is not None else 0, bp, bs, _dt(img), n, h, w, c, flags,
+                                        _p(out), _p(stats), _p(ws), _stream(img))
+        else:
+            C.backend().mgc_hair_lab_balanced_fwd(_p(img), _p(ref), ref.stride(0) if ref is not None else 0, fp, fs, rp, rs,
+                                                  _p(tgt), tgt.stride(0) if tgt is not None else 0, bp, bs, _p(table), _dt(img), n, h, w, c, flags,
+                                                  _p(out), _p(stats), _p(ws), _stream(img))
         ctx.save_for_backward(img, hair_tag, tgt, back, stats)
-        ctx.flags = flags
+        ctx.flags, ctx.balanced = flags, table is not None
         ctx.set_materialize_grads(False)
         return out[0], out[1]
 
@@ -1964,31 +2036,39 @@ class _HairLabLossFn(torch.autograd.Function):
     def backward(ctx, g_hair, g_back):
         img, hair_tag, tgt, back, stats = ctx.saved_tensors
         if g_hair is None and g_back is None:
-            return (None,) * 7
+            return (None,) * 8
         n, h, w, c = img.shape
         g_hair, g_back = _f32_grads(g_hair, g_back)
         (fp, fs), (bp, bs) = _plane_args(hair_tag), _plane_args(back)
         d = torch.empty_like(img)
-        C.backend().mg_hair_lab_bwd(_p(img), fp, fs, _p(tgt), tgt.stride(0) if tgt is not None else 0, bp, bs, _p(stats),
-                                    _p(g_hair), _p(g_back), _dt(img), n, h, w, c, ctx.flags, _p(d), _stream(img))
-        return (d,) + (None,) * 6
+        bwd = C.backend().mgc_hair_lab_balanced_bwd if ctx.balanced else C.backend().mg_hair_lab_bwd
+        bwd(_p(img), fp, fs, _p(tgt), tgt.stride(0) if tgt is not None else 0, bp, bs, _p(stats),
+            _p(g_hair), _p(g_back), _dt(img), n, h, w, c, ctx.flags, _p(d), _stream(img))
+        return (d,) + (None,) * 7
 
 
 def hair_lab_losses(fake: torch.Tensor, image_ref: Optional[torch.Tensor], hair_tag: Optional[torch.Tensor],
                     hair_ref: Optional[torch.Tensor], image_tag: Optional[torch.Tensor] = None, back: Optional[torch.Tensor] = None,
-                    flags: int = HAIR_LAB):
-    """(hairAvgLab, background) of the unpaired stage's generator objective (HairAvgLabLoss loss.py:534-621 without balance_Lab,
+                    flags: int = HAIR_LAB, table: Optional[torch.Tensor] = None):
+    """(hairAvgLab, background) of the unpaired stage's generator objective (HairAvgLabLoss loss.py:534-621,
     RGBBackgroundL1Loss loss.py:388-400; pix2pix_model.py:352-363) in one pass: fake NHWC [N, H, W, C >= 3] bf16 / fp32 with RGB in
     channels 0..2, image_ref / image_tag NCHW [N, 3, H, W], hair_tag / hair_ref / back fp32 [N, H, W] views (channel 1 of the tag label,
     channel 1 of the reference label, channel 0 of the tag label).  `flags`: HAIR_LAB | HAIR_BACKGROUND; a term not selected is 0, costs
     nothing and its operands may be None.  Two fp32 scalars (views of one tensor), gradient to `fake` only.  Two launches forward, one
-    backward."""
+    backward.
+    `table` (lab_weight_table; any fp32 [256, 256] is read as it stands) selects the --balance_Lab weighting: sample n's |da| + |db|
+    counts w_n = table[bin a][bin b] times, the bins taken of the REFERENCE image's mean hair colour; a zero of the table gives weight
+    0 (no replacement here, unlike color_losses).  It needs HAIR_LAB.  Without a table the call is the unbalanced one."""
     flags = int(flags)
     if not 1 <= flags <= 3:
         raise ValueError("hair_lab_losses: flags must select at least one of HAIR_LAB, HAIR_BACKGROUND")
     if fake.dim() != 4 or fake.shape[-1] < 3:
         raise ValueError(f"hair_lab_losses: expected an NHWC image with at least 3 channels, got {tuple(fake.shape)}")
     n, h, w = fake.shape[0], fake.shape[1], fake.shape[2]
+    if table is not None:
+        if not flags & HAIR_LAB:
+            raise ValueError("hair_lab_losses: a weight table needs HAIR_LAB: it weights that term")
+        table = _lab_table(table, "hair_lab_losses", fake)
 
     def image(t, name):
         if t is None:
@@ -2007,7 +2087,7 @@ def hair_lab_losses(fake: torch.Tensor, image_ref: Optional[torch.Tensor], hair_
         image_tag, back = image(image_tag, "image_tag"), _f32_plane(back, "hair_lab_losses: the background plane", (n, h, w))
     else:
         image_tag = back = None
-    return _HairLabLossFn.apply(fake, image_ref, hair_tag, hair_ref, image_tag, back, flags)
+    return _HairLabLossFn.apply(fake, image_ref, hair_tag, hair_ref, image_tag, back, flags, table)
 
 
 FEAT_STYLE, FEAT_CONTENT = 1, 2                       # `flags` bits of mg_feat_moment_loss_*

@@ -64,6 +64,8 @@ def build_parser(is_train: bool = True) -> argparse.ArgumentParser:
                            help="(the second spelling is the reference README's)")
         elif isinstance(value, bool):
             p.add_argument("--" + key, nargs="?", const=True, type=str2bool, default=False if key in flags else value)
+        elif value is None:                                               # a path with no default (weight_dir)
+            p.add_argument("--" + key, type=str, default=None)
         else:
             p.add_argument("--" + key, type=type(value), default=value)
     # the loader's options (options/base_options.py, data/custom_dataset.py, data/pix2pix_dataset.py)
