@@ -165,9 +165,17 @@ __global__ void maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, i
         const size_t base = (((size_t)b * H + 2 * oy) * W + 2 * ox) * C + qd * 4;
         const f32x4_t a = ET<T>::load4(x + base), bq = ET<T>::load4(x + base + C);
         const f32x4_t c = ET<T>::load4(x + base + (size_t)W * C), e = ET<T>::load4(x + base + (size_t)W * C + C);
+        // the FIRST maximum in scan order, the element maxpool_bwd_kernel routes to and the one nn.MaxPool2d keeps: of a -0 and a +0
+        // that tie for the maximum it is whichever comes first (fmaxf orders -0 below +0 and would always answer +0)
         f32x4_t o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = fmaxf(fmaxf(a[j], bq[j]), fmaxf(c[j], e[j]));
+        for (int j = 0; j < 4; ++j) {
+            float m = a[j];
+            if (bq[j] > m) m = bq[j];
+            if (c[j] > m) m = c[j];
+            if (e[j] > m) m = e[j];
+            o[j] = m;
+        }
         ET<T>::store4(y + i * 4, o);
     }
 }

@@ -358,7 +358,12 @@ class EmulatorBackend:
         td = _TD[dtype]
         Ho, Wo = H // 2, W // 2
         xv = _view(x, (N, H, W, C), td)[:, :2 * Ho, :2 * Wo].reshape(N, Ho, 2, Wo, 2, C)
-        _view(y, (N, Ho, Wo, C), td)[:] = xv.amax((2, 4))
+        win = xv.permute(0, 1, 3, 5, 2, 4).reshape(N, Ho, Wo, C, 4)
+        # nn.MaxPool2d keeps the first element in scan order that nothing later exceeds: of a -0 and a +0 the one that comes first
+        best = win[..., 0].clone()
+        for k in range(1, 4):
+            best = torch.where(win[..., k].float() > best.float(), win[..., k], best)
+        _view(y, (N, Ho, Wo, C), td)[:] = best
         return 0
 
     def mg_assemble_nhwc8(self, planar, cp, nhwc, cs, cf, out, dtype, N, HW, stream=None):
@@ -397,7 +402,7 @@ class EmulatorBackend:
         full = torch.zeros((N, H, W, C))
         full[:, :2 * Ho, :2 * Wo] = g.reshape(N, Ho, Wo, C, 2, 2).permute(0, 1, 4, 2, 5, 3).reshape(N, 2 * Ho, 2 * Wo, C)
         if relu_input:
-            full = full * (_view(x, (N, H, W, C), td).float() > 0)
+            full = torch.where(_view(x, (N, H, W, C), td).float() > 0, full, torch.zeros_like(full))     # +0 where the ReLU was off, whatever dy's sign
         _view(dx, (N, H, W, C), td)[:] = full.to(td)
         return 0
 
@@ -655,16 +660,22 @@ class EmulatorBackend:
         return 0
 
     def mg_adam_step(self, param, grad, m, v, numel, lr, b1, b2, eps, step, gscale, stream=None):
+        """torch.optim.Adam's update in float64 on the fp32 values the `float` arguments of the C ABI carry, one rounding per output.
+        exp_avg is torch's two-branch lerp: at beta1 = 0 it is the scaled gradient exactly."""
+        lr, b1, b2, eps, gscale = (ctypes.c_float(t).value for t in (lr, b1, b2, eps, gscale))
         p = _view(param, (numel,), torch.float32)
-        g = _view(grad, (numel,), torch.float32) * gscale
+        g = _view(grad, (numel,), torch.float32).double() * gscale
         mm = _view(m, (numel,), torch.float32)
         vv = _view(v, (numel,), torch.float32)
-        mm.lerp_(g, 1 - b1)
-        vv.mul_(b2).addcmul_(g, g, value=1 - b2)
+        m0, w = mm.double(), 1 - b1
+        m1 = (m0 + w * (g - m0)) if w < 0.5 else (g - (g - m0) * (1 - w))
+        v1 = vv.double() * b2 + g * g * (1 - b2)
         bc1 = 1 - b1 ** step
         bc2 = 1 - b2 ** step
-        denom = vv.sqrt() / math.sqrt(bc2) + eps
-        p.addcdiv_(mm, denom, value=-lr / bc1)
+        denom = v1.sqrt() / math.sqrt(bc2) + eps
+        p[:] = (p.double() - lr / bc1 * (m1 / denom)).float()
+        mm[:] = m1.float()
+        vv[:] = v1.float()
         return 0
 
     # -- input pipeline (SURVEY 8f rank 4): the contract is the reference restatement in oracle/inputs_oracle.py --
